@@ -10,6 +10,12 @@ JSON line from rank 0.
 
 Launch for N>1: torchrun --nnodes=1 --nproc-per-node N bench.py --gpus N ...
 (reads RANK/LOCAL_RANK/WORLD_SIZE/MASTER_* from the env; RCCL backend).
+
+A plain run only sets up, warms up, times the K steps and prints the result
+line.  `--dump-outputs DIR` additionally writes what the last timed step
+computed (see dump_outputs) so two builds can be compared output for output;
+the inputs depend only on the arguments.  `--full` is where any measurement
+beyond the headline figure belongs; there is none today, so it adds nothing.
 """
 
 import argparse
@@ -17,6 +23,7 @@ import json
 import os
 import time
 
+import numpy as np
 import torch
 
 
@@ -45,6 +52,12 @@ def parse_args():
     p.add_argument("--table-size-cap", type=int, default=None,
                    help="cap vocab sizes (CPU smoke only — a capped run is "
                         "NOT a valid benchmark measurement)")
+    p.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                   help="after the timed steps write the last step's outputs "
+                        "(loss, logits, updated parameters) as DIR/<name>.npy")
+    p.add_argument("--full", action="store_true", default=False,
+                   help="also run the measurements beyond the headline figure "
+                        "(none today: a plain run already does only that)")
     return p.parse_args()
 
 
@@ -118,6 +131,53 @@ def maybe_enable_tunableop():
         print(f"# tunableop unavailable: {e}")
 
 
+DUMP_FULL_PARAM_ELEMS = 4 * 1024 * 1024   # larger parameters are sampled
+DUMP_SAMPLE_ROWS = 2048                   # seeded row sample of a large one
+DUMP_TOUCHED_ROWS = 256                   # per table, rows the last step hit
+DUMP_MAX_BYTES = 64 * 1024 * 1024
+
+
+def dump_outputs(out_dir, model, loss, logits, cats, rank, world):
+    """Writes what the last timed step handed back as ``<name>.npy`` (fp32).
+
+    A caller of the train step receives the loss, the logits and the updated
+    parameters.  Small parameters are written whole.  A parameter above
+    DUMP_FULL_PARAM_ELEMS (the fused embedding variables, tens of GB) is
+    written as a fixed seeded sample of DUMP_SAMPLE_ROWS rows, and for every
+    table inside a fused variable the rows looked up by the first
+    DUMP_TOUCHED_ROWS samples of the last batch are written too, so the
+    sparse update of that very step is covered.  ``cats`` is that batch.
+    """
+    arrays = {"loss": loss.detach().reshape(1), "logits": logits.detach()}
+    for pname, prm in model.named_parameters():
+        w = prm.detach()
+        if w.numel() <= DUMP_FULL_PARAM_ELEMS:
+            arrays[f"param.{pname}"] = w
+            continue
+        w2 = w.reshape(w.shape[0], -1)
+        g = torch.Generator(device="cpu").manual_seed(4321)
+        rows = torch.randint(0, w2.shape[0], (DUMP_SAMPLE_ROWS,), generator=g)
+        arrays[f"param_sample.{pname}"] = w2[rows.sort().values.to(w.device)]
+    emb = getattr(model, "embeddings", None)
+    # only where feature i reads table i (DLRM: no shared tables)
+    if emb is not None and world == 1 and \
+            list(emb.strategy.input_table_map) == list(range(len(cats))):
+        groups = emb.strategy.local_concat_groups(rank)
+        for grp, lyr in zip(groups, emb.col_layers):
+            for m in grp.members:
+                ids = cats[m.table_id].reshape(-1)[:DUMP_TOUCHED_ROWS]
+                ids = ids.to(lyr.weight.device) + m.concat_row_offset
+                arrays[f"emb_rows.table{m.table_id:02d}"] = lyr.weight.detach()[ids]
+    prefix = "" if world == 1 else f"rank{rank}."
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, t in arrays.items():
+        a = t.float().cpu().numpy().astype(np.float32, copy=False)
+        total += a.nbytes
+        assert total <= DUMP_MAX_BYTES, f"dump exceeds {DUMP_MAX_BYTES} bytes at {name}"
+        np.save(os.path.join(out_dir, f"{prefix}{name}.npy"), a)
+
+
 def main():
     args = parse_args()
     rank, world, local_rank = setup_dist(args)
@@ -146,8 +206,11 @@ def main():
             cat_shapes = [c.shape for c in cats]
             cat_sizes = [c.numel() for c in cats]
         flat = torch.cat([c.reshape(-1) for c in cats])
-        num = torch.rand(b, num_numerical, device=device)
-        labels = torch.randint(0, 2, (b, 1), device=device).float()
+        # dense inputs and labels come from the same per-entry CPU generator,
+        # so the inputs depend on the arguments alone (not on how many device
+        # random numbers the model's initialisation consumed)
+        num = torch.rand(b, num_numerical, generator=g).to(device)
+        labels = torch.randint(0, 2, (b, 1), generator=g).float().to(device)
         pool.append((num, flat, labels))
 
     def carve(flat):
@@ -177,7 +240,7 @@ def main():
             loss = loss_fn(logits.float(), labels)
         loss.backward()
         opt.step()
-        return loss
+        return loss, logits
 
     graph = None
     graph_ok = torch.cuda.is_available() and (
@@ -193,7 +256,9 @@ def main():
             torch.cuda.synchronize()  # graph block runs on GPU only
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
-                run_fwd_bwd_opt(s_num, s_cats, s_labels, set_to_none=False)
+                # static outputs: every replay rewrites them in place
+                s_out = run_fwd_bwd_opt(s_num, s_cats, s_labels,
+                                        set_to_none=False)
             graph = g
         except Exception as e:
             print(f"# graph capture failed ({type(e).__name__}: {e}); eager fallback")
@@ -206,7 +271,7 @@ def main():
             s_flat.copy_(flat)
             s_labels.copy_(labels)
             graph.replay()
-            return None
+            return s_out
         return run_fwd_bwd_opt(num, carve(flat), labels)
 
     for i in range(args.warmup):
@@ -216,8 +281,9 @@ def main():
     if torch.cuda.is_available():
         torch.cuda.synchronize()
     t0 = time.perf_counter()
+    out = None
     for i in range(args.steps):
-        step(i)
+        out = step(i)
     de.comm.barrier()
     if torch.cuda.is_available():
         torch.cuda.synchronize()
@@ -229,6 +295,11 @@ def main():
         import torch.distributed as dist
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t.item())
+
+    if args.dump_outputs and out is not None:
+        last_flat = pool[(args.steps - 1) % len(pool)][1]
+        dump_outputs(args.dump_outputs, model, out[0], out[1],
+                     carve(last_flat), rank, world)
 
     global_batch = b * world
     samples_per_sec = global_batch * args.steps / elapsed

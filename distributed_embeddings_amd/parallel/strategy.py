@@ -97,7 +97,9 @@ def _pow2_num_slices(elements: int, threshold: Optional[float]) -> int:
         return 1
     n = 1
     size = float(elements)
-    while size > threshold:
+    # below one element n already exceeds every width it is clamped to, and a
+    # threshold <= 0 (auto threshold of 1-element tables) would never be met
+    while size > threshold and size >= 1.0:
         n *= 2
         size /= 2
     return n

@@ -24,6 +24,13 @@ def _run(script, args, timeout=240):
     return proc.stdout
 
 
+def _cpu_env():
+    """Environment for the world-2 CPU launches: two ranks cannot share one
+    GPU (RCCL refuses it), so on a GPU machine the children see no device and
+    take the same gloo path as on a CPU-only one."""
+    return dict(os.environ, HIP_VISIBLE_DEVICES="-1", CUDA_VISIBLE_DEVICES="-1")
+
+
 def test_dlrm_example_smoke():
     out = _run("dlrm_main.py", ["--batch-size", "128", "--num-batches", "3",
                                 "--embedding-dim", "16",
@@ -74,7 +81,7 @@ def test_synthetic_benchmark_torchrun_world2():
          os.path.join(ROOT, "examples", "synthetic_benchmark.py"),
          "--model", "tiny", "--batch-size", "128",
          "--num-steps", "2", "--warmup", "1"],
-        capture_output=True, text=True, timeout=280, cwd=ROOT)
+        capture_output=True, text=True, timeout=280, cwd=ROOT, env=_cpu_env())
     assert proc.returncode == 0, proc.stderr[-2000:]
     assert "world=2" in proc.stdout and "ms/iteration" in proc.stdout
 
@@ -95,7 +102,7 @@ def test_bench_torchrun_world2_json_contract():
          os.path.join(ROOT, "bench.py"), "--gpus", "2",
          "--table-size-cap", "1000", "--batch-per-gpu", "64",
          "--steps", "2", "--warmup", "1"],
-        capture_output=True, text=True, timeout=280, cwd=ROOT)
+        capture_output=True, text=True, timeout=280, cwd=ROOT, env=_cpu_env())
     assert proc.returncode == 0, proc.stderr[-2000:]
     lines = [l for l in proc.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, proc.stdout  # ONE JSON line, rank 0 only
@@ -107,6 +114,71 @@ def test_bench_torchrun_world2_json_contract():
     assert rec["n_gpus"] == 2 and rec["steps"] == 2
     assert rec["scaling"] == "weak"
     assert rec["config"]["global_batch"] == 128
+
+
+def _bench_dump(out_dir, extra=(), env=None):
+    """One single-process capped bench run with --dump-outputs; returns the
+    result record and the dumped arrays."""
+    import json
+    import numpy as np
+    proc = subprocess.run(
+        [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1",
+         "--table-size-cap", "1000", "--batch-per-gpu", "64",
+         "--steps", "3", "--warmup", "1", "--dump-outputs", str(out_dir)]
+        + list(extra),
+        capture_output=True, text=True, timeout=280, cwd=ROOT, env=env)
+    assert proc.returncode == 0, proc.stderr[-2000:]
+    lines = [l for l in proc.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, proc.stdout
+    arrays = {f[:-4]: np.load(os.path.join(out_dir, f))
+              for f in sorted(os.listdir(out_dir)) if f.endswith(".npy")}
+    return json.loads(lines[0]), arrays
+
+
+def _check_dump(rec, arrays):
+    import numpy as np
+    assert rec["steps"] == 3 and rec["warmup"] == 1
+    assert rec["ms_per_step"] > 0
+    assert abs(rec["value"] * rec["ms_per_step"] / 1000.0 - 64) < 1e-6 * 64
+    assert arrays["loss"].shape == (1,)
+    assert arrays["logits"].shape == (64, 1)
+    assert any(k.startswith("param.bottom_mlp") for k in arrays)
+    assert any(k.startswith("param.top_mlp") for k in arrays)
+    touched = [k for k in arrays if k.startswith("emb_rows.table")]
+    assert len(touched) == 26
+    for k in touched:
+        assert arrays[k].shape == (64, 128), k
+    for k, a in arrays.items():
+        assert a.dtype == np.float32, k
+        assert np.isfinite(a).all(), k
+    assert sum(a.nbytes for a in arrays.values()) <= 64 * 1024 * 1024
+
+
+def test_bench_dump_outputs_repeatable(tmp_path):
+    """--dump-outputs writes the last timed step's loss, logits and updated
+    parameters as float32 .npy; the same arguments give the same inputs, so
+    on CPU (no atomics; a GPU, if there is one, is hidden) two runs dump
+    identical arrays.  --full is accepted
+    and leaves the result line's meaning alone."""
+    import numpy as np
+    rec_a, a = _bench_dump(tmp_path / "a", env=_cpu_env())
+    rec_b, b = _bench_dump(tmp_path / "b", extra=["--full"], env=_cpu_env())
+    assert rec_a["dtype"] == "fp32"
+    _check_dump(rec_a, a)
+    assert sorted(a) == sorted(b)
+    for k in a:
+        np.testing.assert_array_equal(a[k], b[k], err_msg=k)
+    for key in ("metric", "unit", "higher_is_better", "dtype", "steps"):
+        assert rec_a[key] == rec_b[key], key
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_gpu_graph_path(tmp_path):
+    """Same dump through the captured-graph train step on the GPU: the static
+    graph outputs of the last replay are what gets written."""
+    rec, arrays = _bench_dump(tmp_path / "g")
+    assert rec["dtype"] == "bf16"
+    _check_dump(rec, arrays)
 
 
 def test_auc_matches_sklearn():

@@ -81,6 +81,16 @@ def test_auto_column_slice_fewer_tables_than_workers():
         assert plan.rank_slices[r], f"rank {r} got no slice"
 
 
+def test_auto_column_slice_one_element_table_terminates():
+    """A 1x1 table with more workers than tables drives the auto threshold
+    to -1; planning must still end, with the table left unsliced."""
+    plan = DistEmbeddingStrategy([TableConfig(1, 1)], 8)
+    assert [s.width for s in plan.table_slices[0]] == [1]
+    plan = DistEmbeddingStrategy([TableConfig(1, 4), TableConfig(3, 1)], 4)
+    assert sum(s.width for s in plan.table_slices[0]) == 4
+    assert [s.width for s in plan.table_slices[1]] == [1]
+
+
 def test_row_slice_remainder():
     plan = DistEmbeddingStrategy([TableConfig(10, 4)], 3,
                                  row_slice_threshold=1)
