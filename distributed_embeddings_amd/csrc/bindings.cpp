@@ -127,6 +127,79 @@ torch::Tensor row_to_split(torch::Tensor rows, int64_t num_rows) {
   return splits;
 }
 
+// Sorted-segment view of a CSR batch, shared by the sparse backward and the
+// fused update: the ids sorted ascending (OOB masked to the `vocab` sentinel,
+// so last), the source row and mean weight of each sorted position, and one
+// segment per unique valid id.  seg holds num_unique segment starts; each
+// caller finishes seg[num_unique...] from bounds in its own way.
+struct SortedSegments {
+  torch::Tensor sorted_ids;  // [nnz] i64
+  torch::Tensor srow;        // [nnz] i64: row of each sorted id
+  torch::Tensor sw;          // [nnz] f32: 1/len of that row (mean only)
+  torch::Tensor seg;         // [nnz + 1] i64: first num_unique are set
+  torch::Tensor unique_ids;  // [nnz] i64: first num_unique are set
+  torch::Tensor num_unique;  // [1] i32, on the device
+  torch::Tensor bounds;      // [1] i64, on the device: first OOB position
+  float* sw_ptr() const { return sw.defined() ? sw.data_ptr<float>() : nullptr; }
+};
+
+SortedSegments build_sorted_segments(torch::Tensor values,
+                                     torch::Tensor row_splits, int64_t vocab,
+                                     bool mean, hipStream_t stream) {
+  const int64_t nnz = values.numel();
+  const int64_t num_rows = row_splits.numel() - 1;
+  auto i64 = values.options();
+  auto i32 = values.options().dtype(torch::kInt32);
+  auto f32 = values.options().dtype(torch::kFloat32);
+  SortedSegments ss;
+
+  // 1. per-id row ids (+ mean weights keyed by original position).
+  auto row_ids = torch::empty({nnz}, i32);
+  torch::Tensor w;
+  if (mean) w = torch::empty({nnz}, f32);
+  float* w_ptr = mean ? w.data_ptr<float>() : nullptr;
+  launch_expand_row_ids(row_splits.data_ptr<int64_t>(), num_rows, nnz,
+                        row_ids.data_ptr<int32_t>(), w_ptr, mean, stream);
+
+  // 2. mask OOB -> sentinel and radix sort packed (id, position); end_bit
+  // covers [0, vocab] inclusive.
+  ss.sorted_ids = torch::empty({nnz}, i64);
+  auto sorted_pos = torch::empty({nnz}, i32);
+  sort_ids_dispatch(values, vocab, nnz, log2_ceil(vocab + 1), ss.sorted_ids,
+                    sorted_pos, stream);
+  size_t temp_bytes = csr_backward_temp_bytes(nnz);
+  auto temp = torch::empty({(int64_t)temp_bytes}, i64.dtype(torch::kUInt8));
+
+  // 3. permute row ids (+ weights) into sorted order, widened to i64.
+  ss.srow = torch::empty({nnz}, i64);
+  if (mean) ss.sw = torch::empty({nnz}, f32);
+  launch_gather_sorted(sorted_pos.data_ptr<int32_t>(),
+                       row_ids.data_ptr<int32_t>(), w_ptr, nnz,
+                       ss.srow.data_ptr<int64_t>(), ss.sw_ptr(), stream);
+
+  // 4. unique-by-key via head flags + scan.
+  auto head = torch::empty({nnz}, i32);
+  auto pos = torch::empty({nnz}, i32);
+  launch_mark_heads(ss.sorted_ids.data_ptr<int64_t>(), nnz, vocab,
+                    head.data_ptr<int32_t>(), stream);
+  auto err = run_inclusive_scan_i32(temp.data_ptr(), temp_bytes,
+                                    head.data_ptr<int32_t>(),
+                                    pos.data_ptr<int32_t>(), nnz, stream);
+  TORCH_CHECK(err == hipSuccess, "inclusive_scan failed");
+  ss.unique_ids = torch::empty({nnz}, i64);
+  ss.seg = torch::empty({nnz + 1}, i64);
+  ss.num_unique = torch::zeros({1}, i32);
+  launch_scatter_unique(ss.sorted_ids.data_ptr<int64_t>(),
+                        head.data_ptr<int32_t>(), pos.data_ptr<int32_t>(), nnz,
+                        ss.unique_ids.data_ptr<int64_t>(),
+                        ss.seg.data_ptr<int64_t>(),
+                        ss.num_unique.data_ptr<int32_t>(), stream);
+  ss.bounds = torch::empty({1}, i64);
+  launch_find_valid_bounds(ss.sorted_ids.data_ptr<int64_t>(), nnz, vocab,
+                           ss.bounds.data_ptr<int64_t>(), stream);
+  return ss;
+}
+
 std::vector<torch::Tensor> csr_lookup_backward(torch::Tensor grad_out,
                                                torch::Tensor values,
                                                torch::Tensor row_splits,
@@ -137,7 +210,6 @@ std::vector<torch::Tensor> csr_lookup_backward(torch::Tensor grad_out,
                   grad_out.dtype() == torch::kBFloat16,
               "grad_out must be fp32 or bf16");
   const int64_t nnz = values.numel();
-  const int64_t num_rows = row_splits.numel() - 1;
   const int width = (int)grad_out.size(1);
   auto stream = current_stream();
   auto i64 = values.options();
@@ -148,80 +220,26 @@ std::vector<torch::Tensor> csr_lookup_backward(torch::Tensor grad_out,
     return {torch::empty({0}, i64), torch::empty({0, width}, f32)};
   }
 
-  // 1+3 fused below: mask OOB -> sentinel and sort packed (id, pos).
+  auto ss = build_sorted_segments(values, row_splits, vocab, mean, stream);
+  launch_set_seg_end(ss.seg.data_ptr<int64_t>(),
+                     ss.num_unique.data_ptr<int32_t>(),
+                     ss.bounds.data_ptr<int64_t>(), stream);
 
-  // 2. per-id row ids (+ mean weights keyed by original position).
-  auto row_ids = torch::empty({nnz}, i32);
-  torch::Tensor w;
-  float* w_ptr = nullptr;
-  if (mean) {
-    w = torch::empty({nnz}, f32);
-    w_ptr = w.data_ptr<float>();
-  }
-  launch_expand_row_ids(row_splits.data_ptr<int64_t>(), num_rows, nnz,
-                        row_ids.data_ptr<int32_t>(), w_ptr, mean, stream);
+  // the one host sync: number of unique ids (output allocation).
+  const int64_t nu = ss.num_unique.to(torch::kCPU).item<int32_t>();
 
-  // 3. radix sort (ids, position) — end_bit covers [0, vocab] inclusive.
-  auto sorted_ids = torch::empty({nnz}, i64);
-  auto sorted_pos = torch::empty({nnz}, i32);
-  sort_ids_dispatch(values, vocab, nnz, log2_ceil(vocab + 1), sorted_ids,
-                    sorted_pos, stream);
-  size_t temp_bytes = csr_backward_temp_bytes(nnz, vocab);
-  auto temp = torch::empty({(int64_t)temp_bytes},
-                           f32.dtype(torch::kUInt8));
-
-  // 4. permute row ids (+ weights) into sorted order, widened to i64.
-  auto srow = torch::empty({nnz}, i64);
-  torch::Tensor sw;
-  float* sw_ptr = nullptr;
-  if (mean) {
-    sw = torch::empty({nnz}, f32);
-    sw_ptr = sw.data_ptr<float>();
-  }
-  launch_gather_sorted(sorted_pos.data_ptr<int32_t>(),
-                       row_ids.data_ptr<int32_t>(), w_ptr, nnz,
-                       srow.data_ptr<int64_t>(), sw_ptr, stream);
-
-  // 5. unique-by-key via head flags + scan.
-  auto head = torch::empty({nnz}, i32);
-  auto pos = torch::empty({nnz}, i32);
-  launch_mark_heads(sorted_ids.data_ptr<int64_t>(), nnz, vocab,
-                    head.data_ptr<int32_t>(), stream);
-  auto err = run_inclusive_scan_i32(temp.data_ptr(), temp_bytes,
-                               head.data_ptr<int32_t>(),
-                               pos.data_ptr<int32_t>(), nnz, stream);
-  TORCH_CHECK(err == hipSuccess, "inclusive_scan failed");
-
-  auto unique_tmp = torch::empty({nnz}, i64);
-  auto seg_tmp = torch::empty({nnz + 1}, i64);
-  auto num_unique_dev = torch::zeros({1}, i32);
-  launch_scatter_unique(sorted_ids.data_ptr<int64_t>(),
-                        head.data_ptr<int32_t>(), pos.data_ptr<int32_t>(), nnz,
-                        vocab, unique_tmp.data_ptr<int64_t>(),
-                        seg_tmp.data_ptr<int64_t>(),
-                        num_unique_dev.data_ptr<int32_t>(), stream);
-  auto bounds = torch::empty({2}, i64);
-  launch_find_valid_bounds(sorted_ids.data_ptr<int64_t>(), nnz, vocab,
-                           bounds.data_ptr<int64_t>(), stream);
-  launch_set_seg_end(seg_tmp.data_ptr<int64_t>(),
-                     num_unique_dev.data_ptr<int32_t>(),
-                     bounds.data_ptr<int64_t>(), stream);
-
-  // 6. the one host sync: number of unique ids (output allocation).
-  const int64_t nu = num_unique_dev.to(torch::kCPU).item<int32_t>();
-
-  auto unique_ids = unique_tmp.narrow(0, 0, nu).contiguous();
+  auto unique_ids = ss.unique_ids.narrow(0, 0, nu).contiguous();
   auto unique_grad = torch::empty({nu, width}, f32);
   if (nu > 0) {
-    // 7. segmented sum == forward gather-reduce over grad_out rows.
+    // segmented sum == forward gather-reduce over grad_out rows.
     auto long_rows = torch::empty({nu}, i64);
     auto long_count = torch::empty({1}, i32);
     auto work_items = torch::empty({nnz / 64 + 64}, i64);
     auto n_work = torch::empty({1}, i32);
     launch_csr_lookup_forward(grad_out.data_ptr(),
                               grad_out.dtype() == torch::kBFloat16,
-                              srow.data_ptr<int64_t>(),
-                              seg_tmp.data_ptr<int64_t>(), sw_ptr,
+                              ss.srow.data_ptr<int64_t>(),
+                              ss.seg.data_ptr<int64_t>(), ss.sw_ptr(),
                               unique_grad.data_ptr<float>(), false, nu, nnz,
                               grad_out.size(0), width, /*mean=*/false,
                               long_rows.data_ptr<int64_t>(),
@@ -334,53 +352,10 @@ void csr_fused_optimizer_apply(torch::Tensor weight, torch::Tensor state,
   auto i32 = values.options().dtype(torch::kInt32);
   auto f32 = grad_out.options().dtype(torch::kFloat32);
 
-  auto row_ids = torch::empty({nnz}, i32);
-  torch::Tensor w;
-  float* w_ptr = nullptr;
-  if (mean) {
-    w = torch::empty({nnz}, f32);
-    w_ptr = w.data_ptr<float>();
-  }
-  launch_expand_row_ids(row_splits.data_ptr<int64_t>(), num_rows, nnz,
-                        row_ids.data_ptr<int32_t>(), w_ptr, mean, stream);
-  auto sorted_ids = torch::empty({nnz}, i64);
-  auto sorted_pos = torch::empty({nnz}, i32);
-  sort_ids_dispatch(values, vocab, nnz, log2_ceil(vocab + 1), sorted_ids,
-                    sorted_pos, stream);
-  size_t temp_bytes = csr_backward_temp_bytes(nnz, vocab);
-  auto temp = torch::empty({(int64_t)temp_bytes}, f32.dtype(torch::kUInt8));
-  auto srow = torch::empty({nnz}, i64);
-  torch::Tensor sw;
-  float* sw_ptr = nullptr;
-  if (mean) {
-    sw = torch::empty({nnz}, f32);
-    sw_ptr = sw.data_ptr<float>();
-  }
-  launch_gather_sorted(sorted_pos.data_ptr<int32_t>(),
-                       row_ids.data_ptr<int32_t>(), w_ptr, nnz,
-                       srow.data_ptr<int64_t>(), sw_ptr, stream);
-  auto head = torch::empty({nnz}, i32);
-  auto pos = torch::empty({nnz}, i32);
-  launch_mark_heads(sorted_ids.data_ptr<int64_t>(), nnz, vocab,
-                    head.data_ptr<int32_t>(), stream);
-  auto err = run_inclusive_scan_i32(temp.data_ptr(), temp_bytes,
-                               head.data_ptr<int32_t>(),
-                               pos.data_ptr<int32_t>(), nnz, stream);
-  TORCH_CHECK(err == hipSuccess, "inclusive_scan failed");
-  auto unique_tmp = torch::empty({nnz}, i64);
-  auto seg_tmp = torch::empty({nnz + 1}, i64);
-  auto nu_dev = torch::zeros({1}, i32);
-  launch_scatter_unique(sorted_ids.data_ptr<int64_t>(),
-                        head.data_ptr<int32_t>(), pos.data_ptr<int32_t>(), nnz,
-                        vocab, unique_tmp.data_ptr<int64_t>(),
-                        seg_tmp.data_ptr<int64_t>(), nu_dev.data_ptr<int32_t>(),
-                        stream);
-  auto bounds = torch::empty({2}, i64);
-  launch_find_valid_bounds(sorted_ids.data_ptr<int64_t>(), nnz, vocab,
-                           bounds.data_ptr<int64_t>(), stream);
-  launch_pad_seg_offsets(seg_tmp.data_ptr<int64_t>(), nnz,
-                         nu_dev.data_ptr<int32_t>(), bounds.data_ptr<int64_t>(),
-                         stream);
+  auto ss = build_sorted_segments(values, row_splits, vocab, mean, stream);
+  launch_pad_seg_offsets(ss.seg.data_ptr<int64_t>(), nnz,
+                         ss.num_unique.data_ptr<int32_t>(),
+                         ss.bounds.data_ptr<int64_t>(), stream);
   auto long_rows = torch::empty({nnz}, i64);
   auto long_count = torch::empty({1}, i32);
   auto work_items = torch::empty({nnz / 64 + 64}, i64);
@@ -401,13 +376,13 @@ void csr_fused_optimizer_apply(torch::Tensor weight, torch::Tensor state,
     scratch_ptr = scratch.data_ptr<float>();
   }
   launch_sorted_optimizer_update(weight.data_ptr(), wbf16, state_ptr,
-                                 (float)eps, sorted_ids.data_ptr<int64_t>(),
-                                 seg_tmp.data_ptr<int64_t>(),
-                                 srow.data_ptr<int64_t>(), sw_ptr,
+                                 (float)eps, ss.sorted_ids.data_ptr<int64_t>(),
+                                 ss.seg.data_ptr<int64_t>(),
+                                 ss.srow.data_ptr<int64_t>(), ss.sw_ptr(),
                                  grad_out.data_ptr(),
                                  grad_out.dtype() == torch::kBFloat16,
                                  lr.data_ptr<float>(),
-                                 nu_dev.data_ptr<int32_t>(), nnz, width,
+                                 ss.num_unique.data_ptr<int32_t>(), nnz, width,
                                  long_rows.data_ptr<int64_t>(),
                                  long_count.data_ptr<int32_t>(),
                                  work_items.data_ptr<int64_t>(),

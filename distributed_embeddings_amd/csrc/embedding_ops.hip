@@ -1,9 +1,8 @@
 // CDNA4 (gfx950 / MI355X) kernels for distributed_embeddings_amd.
 //
 // Hand-written HIP implementations of the reference's native op set
-// (capabilities of /root/reference/distributed_embeddings/cc/kernels/
-// embedding_lookup_kernels.cu, re-designed for 64-wide wavefronts, LDS and
-// HBM3E — not a port):
+// (capabilities of the reference's cc/kernels/embedding_lookup_kernels.cu,
+// re-designed for 64-wide wavefronts, LDS and HBM3E — not a port):
 //
 //   * csr_lookup_forward  — CSR segmented gather-reduce (K1-K3 equivalent).
 //     Wave64 tiling: width<=64 uses sub-wave tiles (64/TILE rows per wave),
@@ -102,6 +101,19 @@ __device__ __forceinline__ void pt_store2(bf16_t* p, const float* v) {
   s.y = *reinterpret_cast<short*>(&h1);
   *reinterpret_cast<short2*>(p) = s;
 }
+// VEC (4, 2 or 1) contiguous elements with the widest matching access
+template <int VEC, typename T>
+__device__ __forceinline__ void pt_loadv(const T* p, float* o) {
+  if constexpr (VEC == 4) pt_load4(p, o);
+  else if constexpr (VEC == 2) pt_load2(p, o);
+  else o[0] = pt_load(p);
+}
+template <int VEC, typename T>
+__device__ __forceinline__ void pt_storev(T* p, const float* v) {
+  if constexpr (VEC == 4) pt_store4(p, v);
+  else if constexpr (VEC == 2) pt_store2(p, v);
+  else pt_store(p, v[0]);
+}
 
 static inline int next_pow2(int v) {
   int p = 1;
@@ -110,6 +122,119 @@ static inline int next_pow2(int v) {
 }
 
 static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// ---------------------------------------------------------------------------
+// Device helpers shared by the forward, backward and fused-update kernels.
+// ---------------------------------------------------------------------------
+
+// Where the calling lane's wave sits in a 1-D grid of wave64 blocks.
+struct WaveCoord {
+  int lane;
+  int64_t wave_id, n_waves;
+};
+__device__ __forceinline__ WaveCoord wave_coord() {
+  return {(int)(threadIdx.x & (WAVE - 1)),
+          ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6,
+          ((int64_t)gridDim.x * blockDim.x) >> 6};
+}
+
+// Sub-wave tiling: `tile` (pow2 <= WAVE) lanes own one work item, so a wave
+// holds rpw items and lane = sub * tile + tl.  Narrow kernels pass the
+// compile-time TILE, wide kernels the runtime tile_w; kernels that give a
+// whole wave to each item pass WAVE.
+struct TileCoord {
+  int rpw, sub, tl;
+};
+__device__ __forceinline__ TileCoord tile_coord(int lane, int tile) {
+  return {WAVE / tile, lane / tile, lane % tile};
+}
+
+// Wide gather-accumulate: acc[v] = sum over k in [ks, ke) of
+// w[k] * src[idx[k]][col0 + v], in k order.  The dispatch only picks a VEC
+// that divides width and col0 is a multiple of VEC, so col0 < width means
+// all VEC columns are inside the row.  CHECK skips ids outside [0, vocab).
+template <int VEC, bool HAS_W, bool CHECK, typename ST>
+__device__ __forceinline__ void wide_accumulate(
+    const ST* __restrict__ src, const int64_t* __restrict__ idx,
+    const float* __restrict__ w, int64_t vocab, int width, int col0,
+    int64_t ks, int64_t ke, float* acc /* size VEC */) {
+#pragma unroll
+  for (int v = 0; v < VEC; ++v) acc[v] = 0.f;
+  for (int64_t k = ks; k < ke; ++k) {
+    const int64_t i = idx[k];
+    if (CHECK && (i < 0 || i >= vocab)) continue;
+    const float wk = HAS_W ? w[k] : 1.f;
+    float r[VEC];
+    pt_loadv<VEC>(src + i * (int64_t)width + col0, r);
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) acc[v] += wk * r[v];
+  }
+}
+
+// Narrow strided reduce: lane column tl = lane % TILE sums
+// w[k] * src[idx[k]][tl] over k = k0, k0 + KSTRIDE, ... < ke.
+//   KSTRIDE == 1: each TILE-lane sub-tile owns its own segment, k0 = ks.
+//   KSTRIDE == WAVE/TILE: the wave's sub-tiles share one segment
+//     (k0 = ks + sub) and a shuffle fold leaves the total on sub-tile 0.
+// UNROLL (pow2) terms are loaded at once and added as a pairwise tree —
+// (t0+t1)+(t2+t3) for 4, t0+t1 for 2 — before joining the running sum; the
+// summation order is part of each caller's bit-exact contract.
+template <int TILE, int KSTRIDE, int UNROLL, bool HAS_W, bool CHECK,
+          typename ST>
+__device__ __forceinline__ float narrow_reduce(
+    const ST* __restrict__ src, const int64_t* __restrict__ idx,
+    const float* __restrict__ w, int64_t vocab, int width, int64_t ks,
+    int64_t ke, int lane) {
+  static_assert(KSTRIDE == 1 || KSTRIDE == WAVE / TILE, "bad k-stride");
+  const int tl = lane % TILE;
+  auto oob = [&](int64_t i) { return CHECK && (i < 0 || i >= vocab); };
+  auto term = [&](int64_t k, int64_t i) {
+    return (HAS_W ? w[k] : 1.f) * pt_load(&src[i * (int64_t)width + tl]);
+  };
+  float acc = 0.f;
+  if (tl < width) {
+    int64_t k = ks + (KSTRIDE > 1 ? lane / TILE : 0);
+    // UNROLL independent idx->row load chains in flight
+    for (; k + (UNROLL - 1) * KSTRIDE < ke; k += UNROLL * KSTRIDE) {
+      int64_t i[UNROLL];
+      float t[UNROLL];
+#pragma unroll
+      for (int u = 0; u < UNROLL; ++u) i[u] = idx[k + u * KSTRIDE];
+#pragma unroll
+      for (int u = 0; u < UNROLL; ++u)
+        t[u] = oob(i[u]) ? 0.f : term(k + u * KSTRIDE, i[u]);
+#pragma unroll
+      for (int s = 1; s < UNROLL; s *= 2) {
+#pragma unroll
+        for (int u = 0; u < UNROLL; u += 2 * s) t[u] += t[u + s];
+      }
+      acc += t[0];
+    }
+    for (; k < ke; k += KSTRIDE) {
+      const int64_t i = idx[k];
+      if (!oob(i)) acc += term(k, i);
+    }
+  }
+  if constexpr (KSTRIDE > 1) {
+#pragma unroll
+    for (int off = WAVE / 2; off >= TILE; off >>= 1)
+      acc += __shfl_down(acc, off);
+  }
+  return acc;
+}
+
+// SGD: w -= lr * g.   Adagrad: s += g^2; w -= lr * g / (sqrt(s) + eps).
+template <bool ADAGRAD, typename PT>
+__device__ __forceinline__ void apply_row_update(PT* w, float* state, float g,
+                                                 float lr, float eps) {
+  if (ADAGRAD) {
+    const float st = *state + g * g;
+    *state = st;
+    pt_store(w, pt_load(w) - lr * g / (sqrtf(st) + eps));
+  } else {
+    pt_store(w, pt_load(w) - lr * g);
+  }
+}
 
 // ---------------------------------------------------------------------------
 // Forward: CSR segmented gather-reduce.
@@ -140,51 +265,27 @@ __global__ void csr_fwd_narrow(const PT* __restrict__ params,
                                int64_t vocab, int width, int64_t long_thresh,
                                int64_t* __restrict__ long_rows,
                                int32_t* __restrict__ long_count) {
-  constexpr int RPW = WAVE / TILE;
-  const int lane = threadIdx.x & (WAVE - 1);
-  const int sub = lane / TILE;
-  const int tl = lane % TILE;
-  const int64_t wave_id =
-      ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  const int64_t n_waves = ((int64_t)gridDim.x * blockDim.x) >> 6;
-  for (int64_t base = wave_id * RPW; base < num_rows; base += n_waves * RPW) {
-    const int64_t row = base + sub;
-    if (row >= num_rows || tl >= width) continue;
+  const WaveCoord wc = wave_coord();
+  const TileCoord tc = tile_coord(wc.lane, TILE);
+  for (int64_t base = wc.wave_id * tc.rpw; base < num_rows;
+       base += wc.n_waves * tc.rpw) {
+    const int64_t row = base + tc.sub;
+    if (row >= num_rows || tc.tl >= width) continue;
     const int64_t s = splits[row], e = splits[row + 1];
     if (e - s > long_thresh) {
-      pt_store(&out[row * width + tl], 0.f);
-      if (tl == 0) long_rows[atomicAdd(long_count, 1)] = row;
+      pt_store(&out[row * width + tc.tl], 0.f);
+      if (tc.tl == 0) long_rows[atomicAdd(long_count, 1)] = row;
       continue;
     }
-    float acc = 0.f;
-    int64_t k = s;
-    // 4-way unroll: 4 independent idx->row load chains in flight
-    for (; k + 4 <= e; k += 4) {
-      const int64_t i0 = values[k], i1 = values[k + 1];
-      const int64_t i2 = values[k + 2], i3 = values[k + 3];
-      float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-      if (i0 >= 0 && i0 < vocab)
-        a0 = (HAS_W ? per_id_w[k] : 1.f) * pt_load(&params[i0 * width + tl]);
-      if (i1 >= 0 && i1 < vocab)
-        a1 = (HAS_W ? per_id_w[k + 1] : 1.f) * pt_load(&params[i1 * width + tl]);
-      if (i2 >= 0 && i2 < vocab)
-        a2 = (HAS_W ? per_id_w[k + 2] : 1.f) * pt_load(&params[i2 * width + tl]);
-      if (i3 >= 0 && i3 < vocab)
-        a3 = (HAS_W ? per_id_w[k + 3] : 1.f) * pt_load(&params[i3 * width + tl]);
-      acc += (a0 + a1) + (a2 + a3);
-    }
-    for (; k < e; ++k) {
-      const int64_t idx = values[k];
-      if (idx < 0 || idx >= vocab) continue;
-      const float w = HAS_W ? per_id_w[k] : 1.f;
-      acc += w * pt_load(&params[idx * width + tl]);
-    }
+    float acc = narrow_reduce<TILE, 1, 4, HAS_W, true>(
+        params, values, per_id_w, vocab, width, s, e, wc.lane);
     if (MEAN && e > s) acc /= (float)(e - s);
-    pt_store(&out[row * width + tl], acc);
+    pt_store(&out[row * width + tc.tl], acc);
   }
 }
 
-// Wide kernel A: width > 64.  One wave per row; VEC elements per lane.
+// Wide kernel A: width > 64.  tile_w lanes per row, VEC elements per lane:
+// a width-128 VEC-4 table runs 2 rows per wave with every lane loading.
 template <int VEC, bool MEAN, bool HAS_W, typename PT, typename OT>
 __global__ void csr_fwd_wide(const PT* __restrict__ params,
                              const int64_t* __restrict__ values,
@@ -195,72 +296,27 @@ __global__ void csr_fwd_wide(const PT* __restrict__ params,
                              int64_t* __restrict__ long_rows,
                              int32_t* __restrict__ long_count,
                              int tile_w /* pow2 lanes per row, <= WAVE */) {
-  const int lane = threadIdx.x & (WAVE - 1);
-  const int64_t wave_id =
-      ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  const int64_t n_waves = ((int64_t)gridDim.x * blockDim.x) >> 6;
-  // sub-wave tiling: tile_w lanes own one row, so a width-128 VEC-4 table
-  // runs 2 rows per wave with every lane loading (was: half the wave idle).
-  const int rpw = WAVE / tile_w;
-  const int sub = lane / tile_w;
-  const int tl = lane % tile_w;
-  const int chunk = tile_w * VEC;
-  for (int64_t base = wave_id * rpw; base < num_rows; base += n_waves * rpw) {
-    const int64_t row = base + sub;
+  const WaveCoord wc = wave_coord();
+  const TileCoord tc = tile_coord(wc.lane, tile_w);
+  for (int64_t base = wc.wave_id * tc.rpw; base < num_rows;
+       base += wc.n_waves * tc.rpw) {
+    const int64_t row = base + tc.sub;
     if (row >= num_rows) continue;
     const int64_t s = splits[row], e = splits[row + 1];
     if (e - s > long_thresh) {
-      for (int c = tl; c < width; c += tile_w)
+      for (int c = tc.tl; c < width; c += tile_w)
         pt_store(&out[row * width + c], 0.f);
-      if (tl == 0) long_rows[atomicAdd(long_count, 1)] = row;
+      if (tc.tl == 0) long_rows[atomicAdd(long_count, 1)] = row;
       continue;
     }
     const float inv = (MEAN && e > s) ? 1.f / (float)(e - s) : 1.f;
-    for (int cbase = 0; cbase < width; cbase += chunk) {
+    for (int col0 = tc.tl * VEC; col0 < width; col0 += tile_w * VEC) {
       float acc[VEC];
-#pragma unroll
-      for (int v = 0; v < VEC; ++v) acc[v] = 0.f;
-      const int col0 = cbase + tl * VEC;
-      for (int64_t k = s; k < e; ++k) {
-        const int64_t idx = values[k];
-        if (idx < 0 || idx >= vocab) continue;
-        const float w = HAS_W ? per_id_w[k] : 1.f;
-        const PT* rowp = params + idx * (int64_t)width + col0;
-        if (VEC == 4) {
-          if (col0 + 4 <= width) {
-            float r[4];
-            pt_load4(rowp, r);
-            acc[0] += w * r[0]; acc[1] += w * r[1];
-            acc[2] += w * r[2]; acc[3] += w * r[3];
-          } else {
-#pragma unroll
-            for (int v = 0; v < 4; ++v)
-              if (col0 + v < width) acc[v] += w * pt_load(&rowp[v]);
-          }
-        } else if (VEC == 2) {
-          if (col0 + 2 <= width) {
-            float r[2];
-            pt_load2(rowp, r);
-            acc[0] += w * r[0]; acc[1] += w * r[1];
-          } else {
-            if (col0 < width) acc[0] += w * pt_load(&rowp[0]);
-          }
-        } else {
-          if (col0 < width) acc[0] += w * pt_load(&rowp[0]);
-        }
-      }
-      OT* outp = out + row * (int64_t)width + col0;
+      wide_accumulate<VEC, HAS_W, true>(params, values, per_id_w, vocab, width,
+                                        col0, s, e, acc);
 #pragma unroll
       for (int v = 0; v < VEC; ++v) acc[v] *= inv;
-      if (VEC == 4 && col0 + 4 <= width) {
-        pt_store4(outp, acc);
-      } else if (VEC == 2 && col0 + 2 <= width) {
-        pt_store2(outp, acc);
-      } else {
-#pragma unroll
-        for (int v = 0; v < VEC; ++v)
-          if (col0 + v < width) pt_store(&outp[v], acc[v]);
-      }
+      pt_storev<VEC>(out + row * (int64_t)width + col0, acc);
     }
   }
 }
@@ -272,26 +328,46 @@ __global__ void expand_long_work(const int64_t* __restrict__ long_rows,
                                  const int64_t* __restrict__ splits,
                                  int64_t* __restrict__ work_items,
                                  int32_t* __restrict__ n_work) {
-  const int lane = threadIdx.x & (WAVE - 1);
-  const int64_t wave_id = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  const int64_t n_waves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+  const WaveCoord wc = wave_coord();
   const int64_t n_long = *long_count;
-  for (int64_t li = wave_id; li < n_long; li += n_waves) {
+  for (int64_t li = wc.wave_id; li < n_long; li += wc.n_waves) {
     const int64_t row = long_rows[li];
     const int64_t len = splits[row + 1] - splits[row];
     const int64_t chunks = (len + LONG_T - 1) / LONG_T;
     int base = 0;
-    if (lane == 0) base = atomicAdd(n_work, (int32_t)chunks);
+    if (wc.lane == 0) base = atomicAdd(n_work, (int32_t)chunks);
     base = __shfl(base, 0);
-    for (int64_t c = lane; c < chunks; c += WAVE) {
+    for (int64_t c = wc.lane; c < chunks; c += WAVE) {
       work_items[base + c] = (li << 24) | c;
     }
   }
 }
 
-// Kernel B: long rows.  Work item = (long row, LONG_T-chunk); one wave each.
-// NW lanes-per-row tiling matches kernel A (TILE for narrow, full wave for
-// wide).  Partials combine with global atomicAdd (out pre-zeroed by A).
+// One decoded work item: ids [ks, ke) of long row `row` = segment [s, e),
+// which is entry li of the long-row list.
+struct LongChunk {
+  int64_t li, row, s, e, ks, ke;
+};
+__device__ __forceinline__ LongChunk long_chunk(
+    const int64_t* __restrict__ work_items,
+    const int64_t* __restrict__ long_rows, const int64_t* __restrict__ splits,
+    int64_t item) {
+  const int64_t w = work_items[item];
+  LongChunk c;
+  c.li = w >> 24;
+  c.row = long_rows[c.li];
+  c.s = splits[c.row];
+  c.e = splits[c.row + 1];
+  c.ks = c.s + (w & 0xffffff) * LONG_T;
+  c.ke = min(c.ks + (int64_t)LONG_T, c.e);
+  return c;
+}
+
+// Kernel B: long rows.  Work item = (long row, LONG_T-chunk).  Narrow
+// (TILE > 0): one wave per item, all 64 lanes active — the 64/TILE sub-tiles
+// each reduce a strided share of the chunk.  Wide (TILE == 0): tile_w lanes
+// per item as in kernel A.  Partials combine with global atomicAdd (out
+// pre-zeroed by A).
 template <int TILE, int VEC, bool MEAN, bool HAS_W, typename PT>
 __global__ void csr_fwd_long(const PT* __restrict__ params,
                              const int64_t* __restrict__ values,
@@ -302,109 +378,37 @@ __global__ void csr_fwd_long(const PT* __restrict__ params,
                              const int64_t* __restrict__ work_items,
                              const int32_t* __restrict__ n_work_ptr,
                              int tile_w) {
-  const int lane = threadIdx.x & (WAVE - 1);
-  const int64_t wave_id =
-      ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  const int64_t n_waves = ((int64_t)gridDim.x * blockDim.x) >> 6;
-  // wide path (TILE==0): tile_w lanes per work item, 64/tile_w items per wave
-  const int rpw_w = TILE > 0 ? 1 : (WAVE / tile_w);
-  const int sub_w = TILE > 0 ? 0 : (lane / tile_w);
-  const int tl_w = TILE > 0 ? lane : (lane % tile_w);
+  const WaveCoord wc = wave_coord();
+  const TileCoord tc = tile_coord(wc.lane, TILE > 0 ? WAVE : tile_w);
   const int64_t n_items = *n_work_ptr;
-  for (int64_t ibase = wave_id * rpw_w; ibase < n_items;
-       ibase += n_waves * rpw_w) {
-    const int64_t item = ibase + sub_w;
+  for (int64_t ibase = wc.wave_id * tc.rpw; ibase < n_items;
+       ibase += wc.n_waves * tc.rpw) {
+    const int64_t item = ibase + tc.sub;
     if (item >= n_items) continue;
-    const int64_t w_it = work_items[item];
-    const int64_t li = w_it >> 24;
-    const int64_t chunk = w_it & 0xffffff;
-    const int64_t row = long_rows[li];
-    const int64_t s = splits[row], e = splits[row + 1];
-    const int64_t k0 = s + chunk * LONG_T;
-    if (k0 >= e) continue;
-    const float inv = (MEAN && e > s) ? 1.f / (float)(e - s) : 1.f;
+    const LongChunk c = long_chunk(work_items, long_rows, splits, item);
+    if (c.ks >= c.e) continue;
+    const float inv = (MEAN && c.e > c.s) ? 1.f / (float)(c.e - c.s) : 1.f;
+    float* orow = out + c.row * (int64_t)width;
     if constexpr (TILE > 0) {
-      // narrow tiling: all 64 lanes active — each of the 64/TILE sub-tiles
-      // reduces a strided share of the chunk, then cross-sub shuffles fold
-      // the partials into sub 0 before one atomic per column.
-      constexpr int T = TILE > 0 ? TILE : 1;
-      constexpr int NSUB = WAVE / T;
-      const int tl = lane % T;
-      const int sub = lane / T;
-      float acc = 0.f;
-      if (tl < width) {
-        {
-          const int64_t ks = k0;
-          const int64_t ke = min(ks + (int64_t)LONG_T, e);
-          int64_t k = ks + sub;
-          for (; k + 3 * NSUB < ke; k += 4 * NSUB) {
-            const int64_t i0 = values[k], i1 = values[k + NSUB];
-            const int64_t i2 = values[k + 2 * NSUB], i3 = values[k + 3 * NSUB];
-            float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-            if (i0 >= 0 && i0 < vocab)
-              a0 = (HAS_W ? per_id_w[k] : 1.f) * pt_load(&params[i0 * width + tl]);
-            if (i1 >= 0 && i1 < vocab)
-              a1 = (HAS_W ? per_id_w[k + NSUB] : 1.f) *
-                   pt_load(&params[i1 * width + tl]);
-            if (i2 >= 0 && i2 < vocab)
-              a2 = (HAS_W ? per_id_w[k + 2 * NSUB] : 1.f) *
-                   pt_load(&params[i2 * width + tl]);
-            if (i3 >= 0 && i3 < vocab)
-              a3 = (HAS_W ? per_id_w[k + 3 * NSUB] : 1.f) *
-                   pt_load(&params[i3 * width + tl]);
-            acc += (a0 + a1) + (a2 + a3);
-          }
-          for (; k < ke; k += NSUB) {
-            const int64_t idx = values[k];
-            if (idx < 0 || idx >= vocab) continue;
-            const float w = HAS_W ? per_id_w[k] : 1.f;
-            acc += w * pt_load(&params[idx * width + tl]);
-          }
-        }
-      }
-#pragma unroll
-      for (int off = WAVE / 2; off >= T; off >>= 1) {
-        acc += __shfl_down(acc, off);
-      }
-      if (sub == 0 && tl < width) {
-        atomicAdd(&out[row * width + tl], acc * inv);
-      }
+      const float acc = narrow_reduce<TILE, WAVE / TILE, 4, HAS_W, true>(
+          params, values, per_id_w, vocab, width, c.ks, c.ke, wc.lane);
+      if (wc.lane < TILE && wc.lane < width)
+        atomicAdd(&orow[wc.lane], acc * inv);
     } else {
-      constexpr int V = VEC > 0 ? VEC : 1;
-      const int CH = tile_w * V;
-      for (int cbase = 0; cbase < width; cbase += CH) {
-        float acc[V];
+      for (int col0 = tc.tl * VEC; col0 < width; col0 += tile_w * VEC) {
+        float acc[VEC];
+        wide_accumulate<VEC, HAS_W, true>(params, values, per_id_w, vocab,
+                                          width, col0, c.ks, c.ke, acc);
 #pragma unroll
-        for (int v = 0; v < V; ++v) acc[v] = 0.f;
-        const int col0 = cbase + tl_w * V;
-        {
-          const int64_t ks = k0;
-          const int64_t ke = min(ks + (int64_t)LONG_T, e);
-          for (int64_t k = ks; k < ke; ++k) {
-            const int64_t idx = values[k];
-            if (idx < 0 || idx >= vocab) continue;
-            const float w = HAS_W ? per_id_w[k] : 1.f;
-            const PT* rowp = params + idx * (int64_t)width + col0;
-            if (V == 4 && col0 + 4 <= width) {
-              float r[4];
-              pt_load4(rowp, r);
-              acc[0] += w * r[0]; acc[1] += w * r[1];
-              acc[2] += w * r[2]; acc[3] += w * r[3];
-            } else {
-#pragma unroll
-              for (int v = 0; v < V; ++v)
-                if (col0 + v < width) acc[v] += w * pt_load(&rowp[v]);
-            }
-          }
-        }
-        float* outp = out + row * (int64_t)width + col0;
-#pragma unroll
-        for (int v = 0; v < V; ++v)
-          if (col0 + v < width) atomicAdd(&outp[v], acc[v] * inv);
+        for (int v = 0; v < VEC; ++v) atomicAdd(&orow[col0 + v], acc[v] * inv);
       }
     }
   }
 }
+
+// ---------------------------------------------------------------------------
+// Host-side dispatch shared by the forward and fused-update launches.
+// ---------------------------------------------------------------------------
 
 static int pick_grid(int64_t work_items, int block_waves) {
   // >> 256 workgroups to fill 8 XCDs x 32 CUs; cap to bound launch cost.
@@ -414,81 +418,57 @@ static int pick_grid(int64_t work_items, int block_waves) {
   return (int)blocks;
 }
 
-template <int TILE, int VEC, typename PT, typename OT>
-static void launch_csr_pair(const PT* params, const int64_t* values,
-                            const int64_t* splits, const float* per_id_w,
-                            OT* out, int64_t num_rows, int64_t nnz,
-                            int64_t vocab, int width, bool mean,
-                            int64_t* long_rows, int32_t* long_count,
-                            int64_t* work_items, int32_t* n_work,
-                            hipStream_t stream) {
-  const int block = 256, bw = block / WAVE;
-  // wide path: tile_w = pow2 lanes covering one row (rows-per-wave = 64/tile_w)
+// Lanes per row and waves needed to give `rows` rows one tile each.  Narrow
+// (TILE > 0): TILE lanes.  Wide: tile_w = pow2 lanes covering width / VEC.
+struct RowTiling {
+  int tile_w;
+  int64_t row_waves;
+};
+template <int TILE, int VEC>
+static RowTiling row_tiling(int width, int64_t rows) {
   int tile_w = WAVE;
-  if (TILE == 0) {
-    const int lanes_needed = (width + (VEC > 0 ? VEC : 1) - 1) /
-                             (VEC > 0 ? VEC : 1);
-    tile_w = next_pow2(lanes_needed);
+  if constexpr (TILE == 0) {
+    tile_w = next_pow2((width + VEC - 1) / VEC);
     if (tile_w > WAVE) tile_w = WAVE;
   }
-  const int64_t row_waves = TILE > 0
-                                ? cdiv64(num_rows, WAVE / (TILE > 0 ? TILE : 1))
-                                : cdiv64(num_rows, WAVE / tile_w);
-  const dim3 grid(pick_grid(row_waves, bw));
-  // Adaptive long threshold: when there are plenty of rows the chip is full
-  // without splitting, so only true outliers (>4x the average and >LONG_T)
-  // offload; with few rows split aggressively for parallelism.
-  const int64_t ave = num_rows > 0 ? nnz / num_rows : 0;
-  int64_t long_thresh = LONG_T;
-  if (row_waves >= 4096) {
-    long_thresh = 4 * (ave > 0 ? ave : 1);
-    if (long_thresh < LONG_T) long_thresh = LONG_T;
-    if (long_thresh > 8192) long_thresh = 8192;
-  }
-  constexpr bool kFloatOut = std::is_same<OT, float>::value;
-  if (!kFloatOut) {
-    // bf16 out: the long-row combine needs fp32 atomics, so disable the
-    // split — every row reduces in-register in kernel A (callers request
-    // bf16 out only on bounded-hotness forwards)
-    long_thresh = INT64_MAX;
-  }
-  hipMemsetAsync(long_count, 0, sizeof(int32_t), stream);
-  hipMemsetAsync(n_work, 0, sizeof(int32_t), stream);
-#define LA(MEAN, HASW)                                                         \
-  do {                                                                         \
-    if constexpr (TILE > 0)                                                    \
-      hipLaunchKernelGGL(                                                      \
-          (csr_fwd_narrow<(TILE > 0 ? TILE : 1), MEAN, HASW, PT, OT>), grid,   \
-          dim3(block), 0, stream, params, values, splits, per_id_w, out,       \
-          num_rows, vocab, width, long_thresh, long_rows, long_count);         \
-    else                                                                       \
-      hipLaunchKernelGGL(                                                      \
-          (csr_fwd_wide<(VEC > 0 ? VEC : 1), MEAN, HASW, PT, OT>),             \
-          grid, dim3(block), 0, stream, params, values, splits,                \
-          per_id_w, out, num_rows, vocab, width, long_thresh,                  \
-          long_rows, long_count, tile_w);                                      \
-  } while (0)
-#define LB(MEAN, HASW)                                                         \
-  do {                                                                         \
-    if constexpr (kFloatOut) {                                                 \
-      hipLaunchKernelGGL(expand_long_work, dim3(512), dim3(block), 0, stream,  \
-                         long_rows, long_count, splits, work_items, n_work);   \
-      hipLaunchKernelGGL((csr_fwd_long<TILE, VEC, MEAN, HASW, PT>),            \
-                         dim3(2048), dim3(block), 0, stream, params, values,   \
-                         splits, per_id_w, (float*)out, vocab, width,          \
-                         long_rows, work_items, n_work, tile_w);               \
-    }                                                                          \
-  } while (0)
-  if (mean) {
-    if (per_id_w) { LA(true, true); LB(true, true); }
-    else          { LA(true, false); LB(true, false); }
-  } else {
-    if (per_id_w) { LA(false, true); LB(false, true); }
-    else          { LA(false, false); LB(false, false); }
-  }
-#undef LA
-#undef LB
+  return {tile_w, cdiv64(rows, WAVE / (TILE > 0 ? TILE : tile_w))};
 }
+
+template <int N>
+using Int = std::integral_constant<int, N>;
+
+// Calls f(Int<TILE>, Int<VEC>).  Narrow widths get TILE = pow2 >= width and
+// VEC 0; wide ones TILE 0 and the largest VEC of 4, 2, 1 that divides width,
+// which is what lets the kernels drop partial-vector handling.
+template <typename F>
+static void dispatch_width(int width, F&& f) {
+  if (width > 64) {
+    if (width % 4 == 0) f(Int<0>{}, Int<4>{});
+    else if (width % 2 == 0) f(Int<0>{}, Int<2>{});
+    else f(Int<0>{}, Int<1>{});
+    return;
+  }
+  switch (next_pow2(width)) {
+    case 1: f(Int<1>{}, Int<0>{}); break;
+    case 2: f(Int<2>{}, Int<0>{}); break;
+    case 4: f(Int<4>{}, Int<0>{}); break;
+    case 8: f(Int<8>{}, Int<0>{}); break;
+    case 16: f(Int<16>{}, Int<0>{}); break;
+    case 32: f(Int<32>{}, Int<0>{}); break;
+    default: f(Int<64>{}, Int<0>{}); break;
+  }
+}
+
+// Calls f(std::true_type) or f(std::false_type).
+template <typename F>
+static void dispatch_bool(bool b, F&& f) {
+  if (b) f(std::true_type{});
+  else f(std::false_type{});
+}
+
+// Storage type selected by a dispatch_bool tag.
+template <typename IsBf16>
+using storage_t = std::conditional_t<IsBf16::value, bf16_t, float>;
 
 template <typename PT, typename OT>
 static void launch_csr_lookup_forward_t(const PT* params, const int64_t* values,
@@ -499,26 +479,53 @@ static void launch_csr_lookup_forward_t(const PT* params, const int64_t* values,
                                         int64_t* long_rows, int32_t* long_count,
                                         int64_t* work_items, int32_t* n_work,
                                         hipStream_t stream) {
-#define ARGS params, values, splits, per_id_w, out, num_rows, nnz, vocab, \
-             width, mean, long_rows, long_count, work_items, n_work, stream
-  if (width <= 64) {
-    switch (next_pow2(width)) {
-      case 1: launch_csr_pair<1, 0, PT, OT>(ARGS); break;
-      case 2: launch_csr_pair<2, 0, PT, OT>(ARGS); break;
-      case 4: launch_csr_pair<4, 0, PT, OT>(ARGS); break;
-      case 8: launch_csr_pair<8, 0, PT, OT>(ARGS); break;
-      case 16: launch_csr_pair<16, 0, PT, OT>(ARGS); break;
-      case 32: launch_csr_pair<32, 0, PT, OT>(ARGS); break;
-      default: launch_csr_pair<64, 0, PT, OT>(ARGS); break;
+  const dim3 block(256);
+  hipMemsetAsync(long_count, 0, sizeof(int32_t), stream);
+  hipMemsetAsync(n_work, 0, sizeof(int32_t), stream);
+  dispatch_width(width, [&](auto tile, auto vec) {
+    constexpr int TILE = decltype(tile)::value, VEC = decltype(vec)::value;
+    constexpr bool kFloatOut = std::is_same<OT, float>::value;
+    const RowTiling t = row_tiling<TILE, VEC>(width, num_rows);
+    const dim3 grid(pick_grid(t.row_waves, block.x / WAVE));
+    // Adaptive long threshold: when there are plenty of rows the chip is full
+    // without splitting, so only true outliers (>4x the average and >LONG_T)
+    // offload; with few rows split aggressively for parallelism.
+    const int64_t ave = num_rows > 0 ? nnz / num_rows : 0;
+    int64_t long_thresh = LONG_T;
+    if (t.row_waves >= 4096) {
+      long_thresh = 4 * (ave > 0 ? ave : 1);
+      if (long_thresh < LONG_T) long_thresh = LONG_T;
+      if (long_thresh > 8192) long_thresh = 8192;
     }
-  } else if (width % 4 == 0) {
-    launch_csr_pair<0, 4, PT, OT>(ARGS);
-  } else if (width % 2 == 0) {
-    launch_csr_pair<0, 2, PT, OT>(ARGS);
-  } else {
-    launch_csr_pair<0, 1, PT, OT>(ARGS);
-  }
-#undef ARGS
+    // bf16 out: the long-row combine needs fp32 atomics, so disable the
+    // split — every row reduces in-register in kernel A (callers request
+    // bf16 out only on bounded-hotness forwards)
+    if (!kFloatOut) long_thresh = INT64_MAX;
+    dispatch_bool(mean, [&](auto mean_t) {
+      dispatch_bool(per_id_w != nullptr, [&](auto has_w_t) {
+        constexpr bool MEAN = decltype(mean_t)::value;
+        constexpr bool HAS_W = decltype(has_w_t)::value;
+        if constexpr (TILE > 0)
+          hipLaunchKernelGGL((csr_fwd_narrow<TILE, MEAN, HAS_W, PT, OT>), grid,
+                             block, 0, stream, params, values, splits,
+                             per_id_w, out, num_rows, vocab, width,
+                             long_thresh, long_rows, long_count);
+        else
+          hipLaunchKernelGGL((csr_fwd_wide<VEC, MEAN, HAS_W, PT, OT>), grid,
+                             block, 0, stream, params, values, splits,
+                             per_id_w, out, num_rows, vocab, width,
+                             long_thresh, long_rows, long_count, t.tile_w);
+        if constexpr (kFloatOut) {
+          hipLaunchKernelGGL(expand_long_work, dim3(512), block, 0, stream,
+                             long_rows, long_count, splits, work_items, n_work);
+          hipLaunchKernelGGL((csr_fwd_long<TILE, VEC, MEAN, HAS_W, PT>),
+                             dim3(2048), block, 0, stream, params, values,
+                             splits, per_id_w, (float*)out, vocab, width,
+                             long_rows, work_items, n_work, t.tile_w);
+        }
+      });
+    });
+  });
 }
 
 void launch_csr_lookup_forward(const void* params, bool params_bf16,
@@ -528,16 +535,16 @@ void launch_csr_lookup_forward(const void* params, bool params_bf16,
                                int width, bool mean, int64_t* long_rows,
                                int32_t* long_count, int64_t* work_items,
                                int32_t* n_work, hipStream_t stream) {
-#define FWD(PTT, OTT)                                                          \
-  launch_csr_lookup_forward_t<PTT, OTT>(                                       \
-      (const PTT*)params, values, splits, per_id_w, (OTT*)out, num_rows, nnz, \
-      vocab, width, mean, long_rows, long_count, work_items, n_work, stream)
-  if (params_bf16) {
-    if (out_bf16) FWD(bf16_t, bf16_t); else FWD(bf16_t, float);
-  } else {
-    if (out_bf16) FWD(float, bf16_t); else FWD(float, float);
-  }
-#undef FWD
+  dispatch_bool(params_bf16, [&](auto p_bf16) {
+    dispatch_bool(out_bf16, [&](auto o_bf16) {
+      using PT = storage_t<decltype(p_bf16)>;
+      using OT = storage_t<decltype(o_bf16)>;
+      launch_csr_lookup_forward_t((const PT*)params, values, splits, per_id_w,
+                                  (OT*)out, num_rows, nnz, vocab, width, mean,
+                                  long_rows, long_count, work_items, n_work,
+                                  stream);
+    });
+  });
 }
 
 // ---------------------------------------------------------------------------
@@ -575,13 +582,11 @@ template <bool MEAN>
 __global__ void expand_row_ids(const int64_t* __restrict__ splits,
                                int64_t num_rows, int32_t* __restrict__ row_ids,
                                float* __restrict__ w) {
-  const int lane = threadIdx.x & (WAVE - 1);
-  const int64_t wave_id = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  const int64_t n_waves = ((int64_t)gridDim.x * blockDim.x) >> 6;
-  for (int64_t row = wave_id; row < num_rows; row += n_waves) {
+  const WaveCoord wc = wave_coord();
+  for (int64_t row = wc.wave_id; row < num_rows; row += wc.n_waves) {
     const int64_t s = splits[row], e = splits[row + 1];
     const float iw = (MEAN && e > s) ? 1.f / (float)(e - s) : 1.f;
-    for (int64_t k = s + lane; k < e; k += WAVE) {
+    for (int64_t k = s + wc.lane; k < e; k += WAVE) {
       row_ids[k] = (int32_t)row;
       if (MEAN) w[k] = iw;
     }
@@ -602,7 +607,7 @@ __global__ void mark_heads(const int64_t* __restrict__ sorted_ids, int64_t n,
 __global__ void scatter_unique(const int64_t* __restrict__ sorted_ids,
                                const int32_t* __restrict__ head,
                                const int32_t* __restrict__ pos, int64_t n,
-                               int64_t vocab, int64_t* __restrict__ unique_ids,
+                               int64_t* __restrict__ unique_ids,
                                int64_t* __restrict__ seg_offsets,
                                int32_t* __restrict__ num_unique) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -612,42 +617,27 @@ __global__ void scatter_unique(const int64_t* __restrict__ sorted_ids,
     unique_ids[u] = sorted_ids[i];
     seg_offsets[u] = i;
   }
-  if (i == n - 1) {
-    // valid count; trailing OOB ids (sorted last) are excluded by valid_end
-    int32_t nu = pos[i];
-    *num_unique = nu;
-  }
+  // valid count; trailing OOB ids (sorted last) carry no head flag
+  if (i == n - 1) *num_unique = pos[i];
 }
 
-// Find the first OOB position (ids sorted ascending; negatives at front).
-// We instead pre-partition: negatives < 0 sort first, >= vocab last.  Segment
-// end for unique u is seg_offsets[u+1] (or valid_end for the last).
+// *valid_end = first index with id >= vocab.  OOB ids (negatives included)
+// are masked to the `vocab` sentinel before the sort, so they all sort last
+// and the last unique segment ends here.
 __global__ void find_valid_bounds(const int64_t* __restrict__ sorted_ids,
                                   int64_t n, int64_t vocab,
-                                  int64_t* __restrict__ bounds) {
-  // bounds[0] = first index with id >= 0; bounds[1] = first index with id >= vocab
-  const int t = threadIdx.x;
-  if (t == 0) {
-    int64_t lo = 0, hi = n;
-    while (lo < hi) {
-      const int64_t mid = (lo + hi) >> 1;
-      if (sorted_ids[mid] < 0) lo = mid + 1; else hi = mid;
-    }
-    bounds[0] = lo;
-  } else if (t == 1) {
-    int64_t lo = 0, hi = n;
-    while (lo < hi) {
-      const int64_t mid = (lo + hi) >> 1;
-      if (sorted_ids[mid] < vocab) lo = mid + 1; else hi = mid;
-    }
-    bounds[1] = lo;
+                                  int64_t* __restrict__ valid_end) {
+  int64_t lo = 0, hi = n;
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (sorted_ids[mid] < vocab) lo = mid + 1; else hi = mid;
   }
+  *valid_end = lo;
 }
 
-size_t csr_backward_temp_bytes(int64_t nnz, int64_t vocab) {
+size_t csr_backward_temp_bytes(int64_t nnz) {
   // only the head-flag inclusive scan uses rocPRIM temp storage now (the
   // sort is the hand-written radix_sort.hip path)
-  (void)vocab;
   size_t scan_bytes = 0;
   rocprim::inclusive_scan(nullptr, scan_bytes, (const int32_t*)nullptr,
                           (int32_t*)nullptr, (size_t)nnz);
@@ -681,26 +671,18 @@ void launch_expand_row_ids(const int64_t* splits, int64_t num_rows,
                            hipStream_t stream) {
   const int block = 256;
   const int64_t ave = num_rows > 0 ? nnz / num_rows : 0;
-  if (ave <= 16) {
-    int64_t blocks = cdiv64(num_rows, block);
-    if (blocks > 16384) blocks = 16384;
-    if (blocks < 1) blocks = 1;
-    if (mean)
-      hipLaunchKernelGGL(expand_row_ids_thread<true>, dim3((int)blocks),
-                         dim3(block), 0, stream, splits, num_rows, row_ids, w);
+  dispatch_bool(mean, [&](auto mean_t) {
+    constexpr bool MEAN = decltype(mean_t)::value;
+    float* wp = MEAN ? w : nullptr;
+    if (ave <= 16)
+      hipLaunchKernelGGL(expand_row_ids_thread<MEAN>,
+                         dim3(pick_grid(num_rows, block)), dim3(block), 0,
+                         stream, splits, num_rows, row_ids, wp);
     else
-      hipLaunchKernelGGL(expand_row_ids_thread<false>, dim3((int)blocks),
-                         dim3(block), 0, stream, splits, num_rows, row_ids,
-                         nullptr);
-    return;
-  }
-  const int grid = pick_grid(num_rows, block / WAVE);
-  if (mean)
-    hipLaunchKernelGGL(expand_row_ids<true>, dim3(grid), dim3(block), 0,
-                       stream, splits, num_rows, row_ids, w);
-  else
-    hipLaunchKernelGGL(expand_row_ids<false>, dim3(grid), dim3(block), 0,
-                       stream, splits, num_rows, row_ids, nullptr);
+      hipLaunchKernelGGL(expand_row_ids<MEAN>,
+                         dim3(pick_grid(num_rows, block / WAVE)), dim3(block),
+                         0, stream, splits, num_rows, row_ids, wp);
+  });
 }
 
 hipError_t run_inclusive_scan_i32(void* temp, size_t temp_bytes,
@@ -719,13 +701,13 @@ void launch_mark_heads(const int64_t* sorted_ids, int64_t n, int64_t vocab,
 }
 
 void launch_scatter_unique(const int64_t* sorted_ids, const int32_t* head,
-                           const int32_t* pos, int64_t n, int64_t vocab,
-                           int64_t* unique_ids, int64_t* seg_offsets,
-                           int32_t* num_unique, hipStream_t stream) {
+                           const int32_t* pos, int64_t n, int64_t* unique_ids,
+                           int64_t* seg_offsets, int32_t* num_unique,
+                           hipStream_t stream) {
   const int block = 256;
   const int64_t grid = cdiv64(n, block);
   hipLaunchKernelGGL(scatter_unique, dim3((int)grid), dim3(block), 0, stream,
-                     sorted_ids, head, pos, n, vocab, unique_ids, seg_offsets,
+                     sorted_ids, head, pos, n, unique_ids, seg_offsets,
                      num_unique);
 }
 
@@ -805,81 +787,44 @@ void launch_gather_sorted(const int32_t* perm, const int32_t* row_ids,
 
 __global__ void set_seg_end(int64_t* __restrict__ seg_offsets,
                             const int32_t* __restrict__ num_unique,
-                            const int64_t* __restrict__ bounds) {
-  seg_offsets[*num_unique] = bounds[1];
+                            const int64_t* __restrict__ valid_end) {
+  seg_offsets[*num_unique] = *valid_end;
 }
 
 void launch_set_seg_end(int64_t* seg_offsets, const int32_t* num_unique,
-                        const int64_t* bounds, hipStream_t stream) {
+                        const int64_t* valid_end, hipStream_t stream) {
   hipLaunchKernelGGL(set_seg_end, dim3(1), dim3(1), 0, stream, seg_offsets,
-                     num_unique, bounds);
+                     num_unique, valid_end);
 }
 
 void launch_find_valid_bounds(const int64_t* sorted_ids, int64_t n,
-                              int64_t vocab, int64_t* bounds,
+                              int64_t vocab, int64_t* valid_end,
                               hipStream_t stream) {
-  hipLaunchKernelGGL(find_valid_bounds, dim3(1), dim3(2), 0, stream, sorted_ids,
-                     n, vocab, bounds);
+  hipLaunchKernelGGL(find_valid_bounds, dim3(1), dim3(1), 0, stream, sorted_ids,
+                     n, vocab, valid_end);
 }
 
 // Pads seg_offsets[i >= num_unique] to the first OOB position so padded
 // segments are empty and the update kernels need no host-side count.
 __global__ void pad_seg_offsets(int64_t* __restrict__ seg, int64_t n,
                                 const int32_t* __restrict__ num_unique,
-                                const int64_t* __restrict__ bounds) {
+                                const int64_t* __restrict__ valid_end) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i > n) return;
-  if (i >= *num_unique) seg[i] = bounds[1];  // first OOB position
+  if (i >= *num_unique) seg[i] = *valid_end;
 }
 
 void launch_pad_seg_offsets(int64_t* seg, int64_t n, const int32_t* num_unique,
-                            const int64_t* bounds, hipStream_t stream) {
+                            const int64_t* valid_end, hipStream_t stream) {
   const int block = 256;
   hipLaunchKernelGGL(pad_seg_offsets, dim3((int)cdiv64(n + 1, block)),
-                     dim3(block), 0, stream, seg, n, num_unique, bounds);
+                     dim3(block), 0, stream, seg, n, num_unique, valid_end);
 }
 
-// Segment-sum helper: reduces grad_out rows of segment [ks, ke) into
-// acc[V] per lane; NARROW (TILE>0): NSUB=64/TILE sub-tiles split k with a
-// cross-sub shuffle fold afterwards; WIDE: V floats per lane, k unrolled x2.
-template <int TILE, int VEC, bool HAS_W, typename GT>
-__device__ __forceinline__ void seg_grad_reduce(
-    const int64_t* __restrict__ srow, const float* __restrict__ sw,
-    const GT* __restrict__ grad_out, int width, int64_t ks, int64_t ke,
-    int lane, float* acc /* size V */) {
-  if constexpr (TILE > 0) {
-    constexpr int T = TILE > 0 ? TILE : 1;
-    constexpr int NSUB = WAVE / T;
-    const int tl = lane % T;
-    const int sub = lane / T;
-    float a = 0.f;
-    if (tl < width) {
-      int64_t k = ks + sub;
-      for (; k + NSUB < ke; k += 2 * NSUB) {
-        const int64_t r0 = srow[k], r1 = srow[k + NSUB];
-        const float w0 = HAS_W ? sw[k] : 1.f;
-        const float w1 = HAS_W ? sw[k + NSUB] : 1.f;
-        a += w0 * pt_load(&grad_out[r0 * (int64_t)width + tl]) +
-             w1 * pt_load(&grad_out[r1 * (int64_t)width + tl]);
-      }
-      if (k < ke) {
-        a += (HAS_W ? sw[k] : 1.f) *
-             pt_load(&grad_out[srow[k] * (int64_t)width + tl]);
-      }
-    }
-#pragma unroll
-    for (int off = WAVE / 2; off >= T; off >>= 1) a += __shfl_down(a, off);
-    acc[0] = a;  // valid on sub 0 lanes
-  } else {
-    constexpr int V = VEC > 0 ? VEC : 1;
-    const int col0 = lane * V;  // caller loops width chunks externally
-    (void)col0;
-  }
-}
-
-// Short segments: one wave per segment, direct (non-atomic) update.
-// Grid-strides only over the REAL segment count (*nu_ptr), not the padded
-// nnz-sized buffer.
+// Short segments: one wave (narrow) or tile_w lanes (wide) per unique id,
+// direct (non-atomic) update.  Grid-strides only over the REAL segment count
+// (*nu_ptr), not the padded nnz-sized buffer.  srow comes from our own
+// expansion, so the gathers need no bounds check.
 template <int TILE, int VEC, bool HAS_W, bool ADAGRAD, typename PT,
           typename GT>
 __global__ void sorted_opt_update(PT* __restrict__ weight,
@@ -895,90 +840,47 @@ __global__ void sorted_opt_update(PT* __restrict__ weight,
                                   int64_t* __restrict__ long_rows,
                                   int32_t* __restrict__ long_count,
                                   int tile_w) {
-  const int lane = threadIdx.x & (WAVE - 1);
-  const int64_t wave_id = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  const int64_t n_waves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+  const WaveCoord wc = wave_coord();
+  const TileCoord tc = tile_coord(wc.lane, TILE > 0 ? WAVE : tile_w);
   const float lr = *lr_ptr;
-  const int rpw_w = TILE > 0 ? 1 : (WAVE / tile_w);
-  const int sub_w = TILE > 0 ? 0 : (lane / tile_w);
-  const int tl_w = TILE > 0 ? lane : (lane % tile_w);
   const int64_t n_segs = *nu_ptr;
-  for (int64_t rbase = wave_id * rpw_w; rbase < n_segs;
-       rbase += n_waves * rpw_w) {
-    const int64_t r = rbase + sub_w;
+  for (int64_t rbase = wc.wave_id * tc.rpw; rbase < n_segs;
+       rbase += wc.n_waves * tc.rpw) {
+    const int64_t r = rbase + tc.sub;
     if (r >= n_segs) continue;
     const int64_t s = seg[r], e = seg[r + 1];
     if (s >= e) continue;
     if (e - s > long_thresh) {
-      if (tl_w == 0) long_rows[atomicAdd(long_count, 1)] = r;
+      if (tc.tl == 0) long_rows[atomicAdd(long_count, 1)] = r;
       continue;
     }
-    const int64_t uid = sorted_ids[s];
+    const int64_t row0 = sorted_ids[s] * (int64_t)width;
     if constexpr (TILE > 0) {
-      constexpr int T = TILE > 0 ? TILE : 1;
-      float acc[1];
-      seg_grad_reduce<T, 0, HAS_W>(srow, sw, grad_out, width, s, e, lane, acc);
-      const int tl = lane % T;
-      if (lane / T == 0 && tl < width) {
-        const int64_t o = uid * (int64_t)width + tl;
-        if (ADAGRAD) {
-          const float g = acc[0];
-          const float st = state[o] + g * g;
-          state[o] = st;
-          pt_store(&weight[o], pt_load(&weight[o]) - lr * g / (sqrtf(st) + eps));
-        } else {
-          pt_store(&weight[o], pt_load(&weight[o]) - lr * acc[0]);
-        }
+      const float g = narrow_reduce<TILE, WAVE / TILE, 2, HAS_W, false>(
+          grad_out, srow, sw, 0, width, s, e, wc.lane);
+      if (wc.lane < TILE && wc.lane < width) {
+        const int64_t o = row0 + wc.lane;
+        apply_row_update<ADAGRAD>(&weight[o], ADAGRAD ? &state[o] : nullptr, g,
+                                  lr, eps);
       }
     } else {
-      constexpr int V = VEC > 0 ? VEC : 1;
-      const int CH = tile_w * V;
-      for (int cbase = 0; cbase < width; cbase += CH) {
-        float acc[V];
+      for (int col0 = tc.tl * VEC; col0 < width; col0 += tile_w * VEC) {
+        float acc[VEC];
+        wide_accumulate<VEC, HAS_W, false>(grad_out, srow, sw, 0, width, col0,
+                                           s, e, acc);
 #pragma unroll
-        for (int v = 0; v < V; ++v) acc[v] = 0.f;
-        const int col0 = cbase + tl_w * V;
-        for (int64_t k = s; k < e; ++k) {
-          const float w = HAS_W ? sw[k] : 1.f;
-          const GT* gp = grad_out + srow[k] * (int64_t)width + col0;
-          if (V == 4 && col0 + 4 <= width) {
-            float g4[4];
-            pt_load4(gp, g4);
-            acc[0] += w * g4[0]; acc[1] += w * g4[1];
-            acc[2] += w * g4[2]; acc[3] += w * g4[3];
-          } else {
-#pragma unroll
-            for (int v = 0; v < V; ++v)
-              if (col0 + v < width) acc[v] += w * pt_load(&gp[v]);
-          }
-        }
-        if (ADAGRAD) {
-          float* sp = state + uid * (int64_t)width;
-          PT* wp = weight + uid * (int64_t)width;
-#pragma unroll
-          for (int v = 0; v < V; ++v) {
-            if (col0 + v < width) {
-              const float g = acc[v];
-              const float st = sp[col0 + v] + g * g;
-              sp[col0 + v] = st;
-              pt_store(&wp[col0 + v],
-                       pt_load(&wp[col0 + v]) - lr * g / (sqrtf(st) + eps));
-            }
-          }
-        } else {
-          PT* wp = weight + uid * (int64_t)width;
-#pragma unroll
-          for (int v = 0; v < V; ++v)
-            if (col0 + v < width)
-              pt_store(&wp[v + col0], pt_load(&wp[v + col0]) - lr * acc[v]);
+        for (int v = 0; v < VEC; ++v) {
+          const int64_t o = row0 + col0 + v;
+          apply_row_update<ADAGRAD>(&weight[o], ADAGRAD ? &state[o] : nullptr,
+                                    acc[v], lr, eps);
         }
       }
     }
   }
 }
 
-// Long segments, SGD: chunk partials atomically into the weight (linear).
-// Long segments, Adagrad: chunk partials into scratch rows, then finalize.
+// Long segments, fp32 SGD: chunk partials atomically into the weight
+// (linear).  Otherwise: chunk partials into fp32 scratch rows, then finalize.
 template <int TILE, int VEC, bool HAS_W, bool TO_SCRATCH, typename GT>
 __global__ void sorted_opt_long(float* __restrict__ target,  // weight or scratch
                                 const int64_t* __restrict__ sorted_ids,
@@ -991,63 +893,31 @@ __global__ void sorted_opt_long(float* __restrict__ target,  // weight or scratc
                                 const int64_t* __restrict__ work_items,
                                 const int32_t* __restrict__ n_work_ptr,
                                 int tile_w) {
-  const int lane = threadIdx.x & (WAVE - 1);
-  const int64_t wave_id = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  const int64_t n_waves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+  const WaveCoord wc = wave_coord();
+  const TileCoord tc = tile_coord(wc.lane, TILE > 0 ? WAVE : tile_w);
   const float lr = TO_SCRATCH ? 1.f : *lr_ptr;
-  const int rpw_w = TILE > 0 ? 1 : (WAVE / tile_w);
-  const int sub_w = TILE > 0 ? 0 : (lane / tile_w);
-  const int tl_w = TILE > 0 ? lane : (lane % tile_w);
   const int64_t n_items = *n_work_ptr;
-  for (int64_t ibase = wave_id * rpw_w; ibase < n_items;
-       ibase += n_waves * rpw_w) {
-    const int64_t item = ibase + sub_w;
+  for (int64_t ibase = wc.wave_id * tc.rpw; ibase < n_items;
+       ibase += wc.n_waves * tc.rpw) {
+    const int64_t item = ibase + tc.sub;
     if (item >= n_items) continue;
-    const int64_t w_it = work_items[item];
-    const int64_t li = w_it >> 24;
-    const int64_t chunk = w_it & 0xffffff;
-    const int64_t r = long_rows[li];
-    const int64_t s = seg[r], e = seg[r + 1];
-    const int64_t ks = s + chunk * LONG_T;
-    if (ks >= e) continue;
-    const int64_t ke = min(ks + (int64_t)LONG_T, e);
-    const int64_t trow = TO_SCRATCH ? li : sorted_ids[s];
+    const LongChunk c = long_chunk(work_items, long_rows, seg, item);
+    if (c.ks >= c.e) continue;
+    float* trow =
+        target + (TO_SCRATCH ? c.li : sorted_ids[c.s]) * (int64_t)width;
     if constexpr (TILE > 0) {
-      constexpr int T = TILE > 0 ? TILE : 1;
-      float acc[1];
-      seg_grad_reduce<T, 0, HAS_W>(srow, sw, grad_out, width, ks, ke, lane, acc);
-      const int tl = lane % T;
-      if (lane / T == 0 && tl < width) {
-        atomicAdd(&target[trow * (int64_t)width + tl],
-                  TO_SCRATCH ? acc[0] : -lr * acc[0]);
-      }
+      const float g = narrow_reduce<TILE, WAVE / TILE, 2, HAS_W, false>(
+          grad_out, srow, sw, 0, width, c.ks, c.ke, wc.lane);
+      if (wc.lane < TILE && wc.lane < width)
+        atomicAdd(&trow[wc.lane], TO_SCRATCH ? g : -lr * g);
     } else {
-      constexpr int V = VEC > 0 ? VEC : 1;
-      const int CH = tile_w * V;
-      for (int cbase = 0; cbase < width; cbase += CH) {
-        float acc[V];
+      for (int col0 = tc.tl * VEC; col0 < width; col0 += tile_w * VEC) {
+        float acc[VEC];
+        wide_accumulate<VEC, HAS_W, false>(grad_out, srow, sw, 0, width, col0,
+                                           c.ks, c.ke, acc);
 #pragma unroll
-        for (int v = 0; v < V; ++v) acc[v] = 0.f;
-        const int col0 = cbase + tl_w * V;
-        for (int64_t k = ks; k < ke; ++k) {
-          const float w = HAS_W ? sw[k] : 1.f;
-          const GT* gp = grad_out + srow[k] * (int64_t)width + col0;
-          if (V == 4 && col0 + 4 <= width) {
-            float g4[4];
-            pt_load4(gp, g4);
-            acc[0] += w * g4[0]; acc[1] += w * g4[1];
-            acc[2] += w * g4[2]; acc[3] += w * g4[3];
-          } else {
-#pragma unroll
-            for (int v = 0; v < V; ++v)
-              if (col0 + v < width) acc[v] += w * pt_load(&gp[v]);
-          }
-        }
-        float* tp = target + trow * (int64_t)width + col0;
-#pragma unroll
-        for (int v = 0; v < V; ++v)
-          if (col0 + v < width)
-            atomicAdd(&tp[v], TO_SCRATCH ? acc[v] : -lr * acc[v]);
+        for (int v = 0; v < VEC; ++v)
+          atomicAdd(&trow[col0 + v], TO_SCRATCH ? acc[v] : -lr * acc[v]);
       }
     }
   }
@@ -1060,93 +930,17 @@ __global__ void sorted_long_finalize(
     const float* __restrict__ lr_ptr, int width,
     const int64_t* __restrict__ long_rows,
     const int32_t* __restrict__ long_count, const float* __restrict__ scratch) {
-  const int lane = threadIdx.x & (WAVE - 1);
-  const int64_t wave_id = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  const int64_t n_waves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+  const WaveCoord wc = wave_coord();
   const float lr = *lr_ptr;
   const int64_t n_long = *long_count;
-  for (int64_t li = wave_id; li < n_long; li += n_waves) {
-    const int64_t r = long_rows[li];
-    const int64_t uid = sorted_ids[seg[r]];
-    for (int c = lane; c < width; c += WAVE) {
-      const float g = scratch[li * (int64_t)width + c];
+  for (int64_t li = wc.wave_id; li < n_long; li += wc.n_waves) {
+    const int64_t uid = sorted_ids[seg[long_rows[li]]];
+    for (int c = wc.lane; c < width; c += WAVE) {
       const int64_t o = uid * (int64_t)width + c;
-      if (ADAGRAD) {
-        const float s = state[o] + g * g;
-        state[o] = s;
-        pt_store(&weight[o], pt_load(&weight[o]) - lr * g / (sqrtf(s) + eps));
-      } else {
-        pt_store(&weight[o], pt_load(&weight[o]) - lr * g);
-      }
+      apply_row_update<ADAGRAD>(&weight[o], ADAGRAD ? &state[o] : nullptr,
+                                scratch[li * (int64_t)width + c], lr, eps);
     }
   }
-}
-
-
-
-template <int TILE, int VEC, typename PT, typename GT>
-static void launch_sorted_opt_pair(PT* weight, float* state, float eps,
-                                   const int64_t* sorted_ids,
-                                   const int64_t* seg, const int64_t* srow,
-                                   const float* sw, const GT* grad_out,
-                                   const float* lr, const int32_t* nu_ptr,
-                                   int64_t max_segs, int width,
-                                   int64_t* long_rows, int32_t* long_count,
-                                   int64_t* work_items, int32_t* n_work,
-                                   float* long_scratch, bool adagrad,
-                                   hipStream_t stream) {
-  const int block = 256;
-  int tile_w = WAVE;
-  if (TILE == 0) {
-    const int lanes_needed = (width + (VEC > 0 ? VEC : 1) - 1) /
-                             (VEC > 0 ? VEC : 1);
-    tile_w = next_pow2(lanes_needed);
-    if (tile_w > WAVE) tile_w = WAVE;
-  }
-  const int64_t row_waves =
-      TILE > 0 ? cdiv64(max_segs, WAVE / (TILE > 0 ? TILE : 1))
-               : cdiv64(max_segs, WAVE / tile_w);
-  const int grid = pick_grid(row_waves, block / WAVE);
-  // bf16 weights have no atomicAdd: their long-SGD path also goes through the
-  // fp32 scratch + finalize pair.
-  constexpr bool PT_F32 = std::is_same<PT, float>::value;
-  const bool use_scratch = adagrad || !PT_F32;
-#define SU(HASW, ADA)                                                          \
-  hipLaunchKernelGGL((sorted_opt_update<TILE, VEC, HASW, ADA, PT, GT>),        \
-                     dim3(grid), dim3(block), 0, stream, weight, state, eps,   \
-                     sorted_ids, seg, srow, sw, grad_out, lr, nu_ptr,          \
-                     (int64_t)LONG_T, width, long_rows, long_count, tile_w)
-#define SL_SCRATCH(HASW)                                                       \
-  hipLaunchKernelGGL((sorted_opt_long<TILE, VEC, HASW, true, GT>), dim3(2048), \
-                     dim3(block), 0, stream, long_scratch, sorted_ids, seg,    \
-                     srow, sw, grad_out, lr, width, long_rows, work_items,     \
-                     n_work, tile_w)
-#define SL_DIRECT(HASW)                                                        \
-  hipLaunchKernelGGL((sorted_opt_long<TILE, VEC, HASW, false, GT>), dim3(2048),\
-                     dim3(block), 0, stream, (float*)weight, sorted_ids, seg,  \
-                     srow, sw, grad_out, lr, width, long_rows, work_items,     \
-                     n_work, tile_w)
-#define FIN(ADA)                                                               \
-  hipLaunchKernelGGL((sorted_long_finalize<ADA, PT>), dim3(256), dim3(block),  \
-                     0, stream, weight, state, eps, sorted_ids, seg, lr,       \
-                     width, long_rows, long_count, long_scratch)
-  if (adagrad) {
-    if (sw) SU(true, true); else SU(false, true);
-  } else {
-    if (sw) SU(true, false); else SU(false, false);
-  }
-  hipLaunchKernelGGL(expand_long_work, dim3(512), dim3(block), 0, stream,
-                     long_rows, long_count, seg, work_items, n_work);
-  if (use_scratch) {
-    if (sw) SL_SCRATCH(true); else SL_SCRATCH(false);
-    if (adagrad) FIN(true); else FIN(false);
-  } else {
-    if (sw) SL_DIRECT(true); else SL_DIRECT(false);
-  }
-#undef SU
-#undef SL_SCRATCH
-#undef SL_DIRECT
-#undef FIN
 }
 
 template <typename PT, typename GT>
@@ -1157,27 +951,42 @@ static void launch_sorted_optimizer_update_t(
     int64_t max_segs, int width, int64_t* long_rows, int32_t* long_count,
     int64_t* work_items, int32_t* n_work, float* long_scratch, bool adagrad,
     hipStream_t stream) {
-#define ARGS weight, state, eps, sorted_ids, seg, srow, sw, grad_out, lr,    \
-             nu_ptr, max_segs, width, long_rows, long_count, work_items,     \
-             n_work, long_scratch, adagrad, stream
-  if (width <= 64) {
-    switch (next_pow2(width)) {
-      case 1: launch_sorted_opt_pair<1, 0, PT, GT>(ARGS); break;
-      case 2: launch_sorted_opt_pair<2, 0, PT, GT>(ARGS); break;
-      case 4: launch_sorted_opt_pair<4, 0, PT, GT>(ARGS); break;
-      case 8: launch_sorted_opt_pair<8, 0, PT, GT>(ARGS); break;
-      case 16: launch_sorted_opt_pair<16, 0, PT, GT>(ARGS); break;
-      case 32: launch_sorted_opt_pair<32, 0, PT, GT>(ARGS); break;
-      default: launch_sorted_opt_pair<64, 0, PT, GT>(ARGS); break;
-    }
-  } else if (width % 4 == 0) {
-    launch_sorted_opt_pair<0, 4, PT, GT>(ARGS);
-  } else if (width % 2 == 0) {
-    launch_sorted_opt_pair<0, 2, PT, GT>(ARGS);
-  } else {
-    launch_sorted_opt_pair<0, 1, PT, GT>(ARGS);
-  }
-#undef ARGS
+  const dim3 block(256);
+  // bf16 weights have no atomicAdd: their long-SGD path also goes through the
+  // fp32 scratch + finalize pair.
+  const bool use_scratch = adagrad || !std::is_same<PT, float>::value;
+  dispatch_width(width, [&](auto tile, auto vec) {
+    constexpr int TILE = decltype(tile)::value, VEC = decltype(vec)::value;
+    const RowTiling t = row_tiling<TILE, VEC>(width, max_segs);
+    const dim3 grid(pick_grid(t.row_waves, block.x / WAVE));
+    dispatch_bool(sw != nullptr, [&](auto has_w_t) {
+      constexpr bool HAS_W = decltype(has_w_t)::value;
+      dispatch_bool(adagrad, [&](auto ada) {
+        hipLaunchKernelGGL(
+            (sorted_opt_update<TILE, VEC, HAS_W, decltype(ada)::value, PT, GT>),
+            grid, block, 0, stream, weight, state, eps, sorted_ids, seg, srow,
+            sw, grad_out, lr, nu_ptr, (int64_t)LONG_T, width, long_rows,
+            long_count, t.tile_w);
+      });
+      hipLaunchKernelGGL(expand_long_work, dim3(512), block, 0, stream,
+                         long_rows, long_count, seg, work_items, n_work);
+      dispatch_bool(use_scratch, [&](auto to_scratch) {
+        constexpr bool TO_SCRATCH = decltype(to_scratch)::value;
+        hipLaunchKernelGGL(
+            (sorted_opt_long<TILE, VEC, HAS_W, TO_SCRATCH, GT>), dim3(2048),
+            block, 0, stream, TO_SCRATCH ? long_scratch : (float*)weight,
+            sorted_ids, seg, srow, sw, grad_out, lr, width, long_rows,
+            work_items, n_work, t.tile_w);
+      });
+    });
+    if (use_scratch)
+      dispatch_bool(adagrad, [&](auto ada) {
+        hipLaunchKernelGGL((sorted_long_finalize<decltype(ada)::value, PT>),
+                           dim3(256), block, 0, stream, weight, state, eps,
+                           sorted_ids, seg, lr, width, long_rows, long_count,
+                           long_scratch);
+      });
+  });
 }
 
 void launch_sorted_optimizer_update(void* weight, bool weight_bf16,
@@ -1198,27 +1007,24 @@ void launch_sorted_optimizer_update(void* weight, bool weight_bf16,
     hipMemsetAsync(long_scratch, 0,
                    sizeof(float) * scratch_rows * (int64_t)width, stream);
   }
-#define SOU(PTT, GTT)                                                          \
-  launch_sorted_optimizer_update_t<PTT, GTT>(                                  \
-      (PTT*)weight, state, eps, sorted_ids, seg, srow, sw,                     \
-      (const GTT*)grad_out, lr, nu_ptr, max_segs, width, long_rows,            \
-      long_count, work_items, n_work, long_scratch, adagrad, stream)
-  if (weight_bf16) {
-    if (grad_bf16) SOU(bf16_t, bf16_t); else SOU(bf16_t, float);
-  } else {
-    if (grad_bf16) SOU(float, bf16_t); else SOU(float, float);
-  }
-#undef SOU
+  dispatch_bool(weight_bf16, [&](auto w_bf16) {
+    dispatch_bool(grad_bf16, [&](auto g_bf16) {
+      using PT = storage_t<decltype(w_bf16)>;
+      using GT = storage_t<decltype(g_bf16)>;
+      launch_sorted_optimizer_update_t(
+          (PT*)weight, state, eps, sorted_ids, seg, srow, sw,
+          (const GT*)grad_out, lr, nu_ptr, max_segs, width, long_rows,
+          long_count, work_items, n_work, long_scratch, adagrad, stream);
+    });
+  });
 }
 
 // ---------------------------------------------------------------------------
 // Fused sparse optimizer steps: apply (unique_ids, unique_grad) rows directly
 // to the table — no torch sparse re-coalesce, no dense grad materialization.
-// One wave per row (width>64) or sub-wave tiles (narrow), same tiling as the
-// lookup kernels.
+// One wave per row.
 // ---------------------------------------------------------------------------
 
-// SGD: w[id] -= lr * g.   Adagrad: s[id] += g^2; w[id] -= lr*g/(sqrt(s)+eps).
 template <bool ADAGRAD, typename PT>
 __global__ void sparse_row_update(PT* __restrict__ weight,
                                   float* __restrict__ state,
@@ -1226,23 +1032,13 @@ __global__ void sparse_row_update(PT* __restrict__ weight,
                                   const float* __restrict__ grad,
                                   int64_t num_rows, int width, float lr,
                                   float eps) {
-  const int lane = threadIdx.x & (WAVE - 1);
-  const int64_t wave_id = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  const int64_t n_waves = ((int64_t)gridDim.x * blockDim.x) >> 6;
-  for (int64_t r = wave_id; r < num_rows; r += n_waves) {
-    const int64_t row = ids[r];
-    PT* wp = weight + row * (int64_t)width;
-    float* sp = ADAGRAD ? state + row * (int64_t)width : nullptr;
-    const float* gp = grad + r * (int64_t)width;
-    for (int c = lane; c < width; c += WAVE) {
-      const float g = gp[c];
-      if (ADAGRAD) {
-        const float s = sp[c] + g * g;
-        sp[c] = s;
-        pt_store(&wp[c], pt_load(&wp[c]) - lr * g / (sqrtf(s) + eps));
-      } else {
-        pt_store(&wp[c], pt_load(&wp[c]) - lr * g);
-      }
+  const WaveCoord wc = wave_coord();
+  for (int64_t r = wc.wave_id; r < num_rows; r += wc.n_waves) {
+    const int64_t row0 = ids[r] * (int64_t)width;
+    for (int c = wc.lane; c < width; c += WAVE) {
+      const int64_t o = row0 + c;
+      apply_row_update<ADAGRAD>(&weight[o], ADAGRAD ? &state[o] : nullptr,
+                                grad[r * (int64_t)width + c], lr, eps);
     }
   }
 }
@@ -1253,16 +1049,14 @@ void launch_sparse_row_update(void* weight, bool weight_bf16, float* state,
                               bool adagrad, hipStream_t stream) {
   const int block = 256;
   const int grid = pick_grid(num_rows, block / WAVE);
-#define SRU(ADA, PT)                                                         \
-  hipLaunchKernelGGL((sparse_row_update<ADA, PT>), dim3(grid), dim3(block),  \
-                     0, stream, (PT*)weight, state, ids, grad, num_rows,     \
-                     width, lr, eps)
-  if (weight_bf16) {
-    if (adagrad) SRU(true, bf16_t); else SRU(false, bf16_t);
-  } else {
-    if (adagrad) SRU(true, float); else SRU(false, float);
-  }
-#undef SRU
+  dispatch_bool(weight_bf16, [&](auto w_bf16) {
+    dispatch_bool(adagrad, [&](auto ada) {
+      using PT = storage_t<decltype(w_bf16)>;
+      hipLaunchKernelGGL((sparse_row_update<decltype(ada)::value, PT>),
+                         dim3(grid), dim3(block), 0, stream, (PT*)weight,
+                         state, ids, grad, num_rows, width, lr, eps);
+    });
+  });
 }
 
 // ---------------------------------------------------------------------------

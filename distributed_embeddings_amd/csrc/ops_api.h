@@ -18,7 +18,7 @@ void launch_csr_lookup_forward(const void* params, bool params_bf16,
 void launch_row_to_split(const int64_t* rows, int64_t nnz, int64_t num_rows,
                          int64_t* splits, hipStream_t stream);
 
-size_t csr_backward_temp_bytes(int64_t nnz, int64_t vocab);
+size_t csr_backward_temp_bytes(int64_t nnz);
 
 void launch_expand_row_ids(const int64_t* splits, int64_t num_rows,
                            int64_t nnz, int32_t* row_ids, float* w, bool mean,
@@ -32,20 +32,21 @@ void launch_mark_heads(const int64_t* sorted_ids, int64_t n, int64_t vocab,
                        int32_t* head, hipStream_t stream);
 
 void launch_scatter_unique(const int64_t* sorted_ids, const int32_t* head,
-                           const int32_t* pos, int64_t n, int64_t vocab,
-                           int64_t* unique_ids, int64_t* seg_offsets,
-                           int32_t* num_unique, hipStream_t stream);
+                           const int32_t* pos, int64_t n, int64_t* unique_ids,
+                           int64_t* seg_offsets, int32_t* num_unique,
+                           hipStream_t stream);
 
 void launch_gather_sorted(const int32_t* perm, const int32_t* row_ids,
                           const float* w, int64_t n, int64_t* srow, float* sw,
                           hipStream_t stream);
 
-void launch_set_seg_end(int64_t* seg_offsets, const int32_t* num_unique,
-                        const int64_t* bounds, hipStream_t stream);
-
+// *valid_end = first sorted position holding an out-of-vocabulary id.
 void launch_find_valid_bounds(const int64_t* sorted_ids, int64_t n,
-                              int64_t vocab, int64_t* bounds,
+                              int64_t vocab, int64_t* valid_end,
                               hipStream_t stream);
+
+void launch_set_seg_end(int64_t* seg_offsets, const int32_t* num_unique,
+                        const int64_t* valid_end, hipStream_t stream);
 
 void launch_integer_lookup(const int64_t* keys, int64_t n, int64_t* tkeys,
                            int64_t* tvals, int64_t capacity, int32_t* counts,
@@ -61,7 +62,7 @@ void launch_hash_reinsert(const int64_t* old_keys, const int64_t* old_vals,
                           int64_t capacity, hipStream_t stream);
 
 void launch_pad_seg_offsets(int64_t* seg, int64_t n, const int32_t* num_unique,
-                            const int64_t* bounds, hipStream_t stream);
+                            const int64_t* valid_end, hipStream_t stream);
 
 void launch_sorted_optimizer_update(void* weight, bool weight_bf16,
                                     float* state, float eps,

@@ -4,6 +4,8 @@ against the plain-PyTorch fp32 reference of the same op.
 Run via: gpurun -- python -m pytest tests -m gpu -x -q
 """
 
+import functools
+
 import pytest
 import torch
 
@@ -857,3 +859,208 @@ def test_inference_graph_capture_matches_eager():
         torch.cuda.synchronize()
     assert torch.allclose(out, eager, atol=1e-3), \
         float((out - eager).abs().max())
+
+
+# ---------------------------------------------------------------------------
+# Every tiling of the shared gather-reduce helpers, at the smallest shapes
+# that reach it: narrow TILE 4/16/64/64 (widths 3, 16, 33, 64) and wide
+# VEC 1 in two chunks (65), VEC 2 in one chunk (66), VEC 4 with two rows per
+# wave (68), VEC 2 and VEC 4 in two chunks (130, 260).  37 rows divide by no
+# rows-per-wave; lengths 0..7 take the in-register path; one row of 300 takes
+# the long path in three chunks with a ragged last chunk of 44.
+#
+# Tolerances (derived, not tuned), per output element:
+#   * sum of <= 7 terms: atol 1e-4, the kernel tolerance used above;
+#   * sum of up to 300 N(0,1)-sized terms: atol 1e-3 — n * eps * max|x| ~
+#     300 * 6e-8 * 5 ~ 1e-4, with a tenfold margin for the order of the
+#     atomic combine;
+#   * result stored as bf16: plus 2**-8 * |ref|, one RNE rounding.
+# All references are float64; each test also checks that the same reference
+# in fp32 on the CPU stays inside these bounds.
+# ---------------------------------------------------------------------------
+_HELPER_WIDTHS = [3, 16, 33, 64, 65, 66, 68, 130, 260]
+_HELPER_ROWS, _HELPER_VOCAB, _HELPER_LONG_ROW, _HELPER_LONG_LEN = 37, 50, 20, 300
+_HELPER_HOT_ID = _HELPER_VOCAB - 1
+
+
+@functools.lru_cache(maxsize=None)
+def _helper_case():
+    g = torch.Generator().manual_seed(2024)
+    lengths = torch.randint(0, 8, (_HELPER_ROWS,), generator=g)
+    lengths[3], lengths[11], lengths[36] = 0, 7, 5
+    lengths[_HELPER_LONG_ROW] = _HELPER_LONG_LEN
+    splits = torch.cat([torch.zeros(1, dtype=torch.long), lengths.cumsum(0)])
+    nnz = int(splits[-1])
+    lo = int(splits[_HELPER_LONG_ROW])
+    long_pos = slice(lo, lo + _HELPER_LONG_LEN)
+    # short rows never draw the hot id, so in ids_hot it occurs exactly 300x
+    ids = torch.randint(0, _HELPER_HOT_ID, (nnz,), generator=g)
+    ids_rand = ids.clone()
+    ids_rand[long_pos] = torch.randint(0, _HELPER_VOCAB, (_HELPER_LONG_LEN,),
+                                       generator=g)
+    ids_hot = ids.clone()
+    ids_hot[long_pos] = _HELPER_HOT_ID
+    # forward only: out-of-range ids in short rows and in all three chunks
+    ids_oob = ids_rand.clone()
+    ids_oob[int(splits[11])] = -1
+    ids_oob[int(splits[37]) - 1] = _HELPER_VOCAB
+    ids_oob[lo] = -1
+    ids_oob[lo + 130] = _HELPER_VOCAB
+    ids_oob[lo + 299] = _HELPER_VOCAB
+    row_of = torch.repeat_interleave(torch.arange(_HELPER_ROWS), lengths)
+    return dict(lengths=lengths, splits=splits, row_of=row_of,
+                ids_rand=ids_rand, ids_hot=ids_hot, ids_oob=ids_oob)
+
+
+def _terms_atol(n_terms):
+    """[n, 1] absolute tolerance from the number of terms in each sum."""
+    return torch.where(n_terms <= 7, 1e-4, 1e-3).double().unsqueeze(1)
+
+
+@functools.lru_cache(maxsize=None)
+def _helper_dense(width):
+    """N(0,1) [50, width] table and [37, width] upstream grad.  The long
+    row's grad is scaled by 2**-7: with the hot id it enters the sum 300
+    times, so the sum grows like 300 * x instead of the sqrt(300) * x of 300
+    independent terms that the 1e-3 bound is derived for; scaled, |g| stays
+    below ~10 and fp32 can hold the Adagrad state 1 + g*g to that bound."""
+    g = torch.Generator().manual_seed(width)
+    table = torch.randn(_HELPER_VOCAB, width, generator=g)
+    grad = torch.randn(_HELPER_ROWS, width, generator=g)
+    grad[_HELPER_LONG_ROW] *= 2.0 ** -7
+    return table, grad
+
+
+def _forward_ref(table, ids, splits, combiner, dtype):
+    """The algorithm of _csr_lookup_ref (which itself accumulates in fp32)
+    carried out in `dtype`."""
+    lengths = splits[1:] - splits[:-1]
+    valid = (ids >= 0) & (ids < table.shape[0])
+    rows = table.to(dtype)[ids.clamp(0, table.shape[0] - 1)]
+    rows = rows * valid.unsqueeze(1)
+    seg = torch.repeat_interleave(torch.arange(lengths.numel()), lengths)
+    out = torch.zeros(lengths.numel(), table.shape[1], dtype=dtype)
+    out.index_add_(0, seg, rows)
+    if combiner == "mean":
+        out = out / lengths.clamp(min=1).to(dtype).unsqueeze(1)
+    return out
+
+
+def _dense_grad_ref(grad, ids, case, combiner, dtype):
+    """[vocab, width] index_add reference of the sparse backward."""
+    rows = grad.to(dtype)[case["row_of"]]
+    if combiner == "mean":
+        rows = rows / case["lengths"].to(dtype)[case["row_of"]].unsqueeze(1)
+    dense = torch.zeros(_HELPER_VOCAB, grad.shape[1], dtype=dtype)
+    return dense.index_add_(0, ids, rows)
+
+
+def _assert_within(what, got, ref, tol):
+    err = (got.double().cpu() - ref.double()).abs()
+    tol = tol.expand_as(err)
+    print(f"{what}: max err {float(err.max()):.3e}, "
+          f"worst err/tol {float((err / tol).max()):.3f}")
+    assert bool((err <= tol).all()), what
+
+
+@requires_gpu
+@pytest.mark.parametrize("combiner", ["sum", "mean"])
+def test_shared_helpers_forward(combiner):
+    from distributed_embeddings_amd.ops import _backend
+    from distributed_embeddings_amd.ops.embedding_lookup import _csr_lookup_ref
+    ext = _backend.ops()
+    case = _helper_case()
+    ids, splits = case["ids_oob"], case["splits"]
+    atol = _terms_atol(case["lengths"])
+    for width in _HELPER_WIDTHS:
+        for tdt in (torch.float32, torch.bfloat16):
+            table = _helper_dense(width)[0].to(tdt)
+            ref = _forward_ref(table, ids, splits, combiner, torch.float64)
+            _assert_within(f"cpu fp32 w{width} {tdt}",
+                           _csr_lookup_ref(table, ids, splits, combiner),
+                           ref, atol)
+            for out_bf16 in (False, True):
+                out = ext.csr_lookup_forward(table.cuda(), ids.cuda(),
+                                             splits.cuda(), combiner == "mean",
+                                             out_bf16)
+                assert out.dtype == (torch.bfloat16 if out_bf16
+                                     else torch.float32)
+                tol = atol + (2.0 ** -8 * ref.abs() if out_bf16 else 0.0)
+                _assert_within(f"fwd w{width} {tdt} out_bf16={out_bf16}",
+                               out, ref, tol)
+
+
+@requires_gpu
+@pytest.mark.parametrize("combiner", ["sum", "mean"])
+def test_shared_helpers_backward(combiner):
+    """ids_rand is the forward's shape; ids_hot adds a 300-long unique
+    segment, which takes the weighted long path."""
+    from distributed_embeddings_amd.ops import _backend
+    ext = _backend.ops()
+    case = _helper_case()
+    splits = case["splits"].cuda()
+    for which in ("ids_rand", "ids_hot"):
+        ids = case[which]
+        uniq, counts = torch.unique(ids, return_counts=True)
+        atol = _terms_atol(counts)
+        for width in _HELPER_WIDTHS:
+            for gdt in (torch.float32, torch.bfloat16):
+                grad = _helper_dense(width)[1].to(gdt)
+                ref = _dense_grad_ref(grad, ids, case, combiner,
+                                      torch.float64)[uniq]
+                ref32 = _dense_grad_ref(grad, ids, case, combiner,
+                                        torch.float32)[uniq]
+                _assert_within(f"cpu fp32 {which} w{width} {gdt}", ref32, ref,
+                               atol)
+                u, g = ext.csr_lookup_backward(grad.cuda(), ids.cuda(), splits,
+                                               _HELPER_VOCAB,
+                                               combiner == "mean")
+                assert torch.equal(u.cpu(), uniq)
+                assert g.dtype == torch.float32
+                _assert_within(f"bwd {which} w{width} {gdt}", g, ref, atol)
+
+
+@requires_gpu
+@pytest.mark.parametrize("combiner", ["sum", "mean"])
+@pytest.mark.parametrize("method", ["sgd", "adagrad"])
+def test_shared_helpers_fused_update(method, combiner):
+    """One id occurs 300 times: fp32 SGD takes the direct-atomic long path,
+    Adagrad and bf16 weights the scratch + finalize one."""
+    from distributed_embeddings_amd.ops import _backend
+    ext = _backend.ops()
+    case = _helper_case()
+    ids, splits = case["ids_hot"], case["splits"].cuda()
+    adagrad = method == "adagrad"
+    lr = torch.tensor([0.125])
+    eps = float(torch.tensor(1e-10, dtype=torch.float32))
+    atol = _terms_atol(torch.bincount(ids, minlength=_HELPER_VOCAB))
+    for width in _HELPER_WIDTHS:
+        table, grad = _helper_dense(width)
+        for wdt in (torch.float32, torch.bfloat16):
+            for gdt in (torch.float32, torch.bfloat16):
+                w0, gq = table.to(wdt), grad.to(gdt)
+                g64 = _dense_grad_ref(gq, ids, case, combiner, torch.float64)
+                g32 = _dense_grad_ref(gq, ids, case, combiner, torch.float32)
+
+                def step(g):  # the update in g's precision
+                    st = 1.0 + g * g
+                    d = g / (st.sqrt() + eps) if adagrad else g
+                    return w0.to(g.dtype) - float(lr) * d, st
+
+                w_ref, st_ref = step(g64)
+                w_tol = atol + (2.0 ** -8 * w_ref.abs()
+                                if wdt == torch.bfloat16 else 0.0)
+                tag = f"{method} {combiner} w{width} {wdt} {gdt}"
+                w32, st32 = step(g32)
+                _assert_within(f"cpu fp32 weight {tag}", w32, w_ref, w_tol)
+                w = w0.cuda()
+                state = torch.ones(_HELPER_VOCAB, width, device="cuda")
+                ext.csr_fused_optimizer_apply(w, state, ids.cuda(), splits,
+                                              gq.cuda(), lr.cuda(),
+                                              combiner == "mean", adagrad, eps)
+                _assert_within(f"weight {tag}", w, w_ref, w_tol)
+                if adagrad:
+                    _assert_within(f"cpu fp32 state {tag}", st32, st_ref, atol)
+                    _assert_within(f"state {tag}", state, st_ref, atol)
+                else:
+                    assert bool((state == 1.0).all()), "SGD touched the state"
