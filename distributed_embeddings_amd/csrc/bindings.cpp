@@ -483,6 +483,36 @@ torch::Tensor dot_interact_bwd(torch::Tensor gout, torch::Tensor feats) {
   return gfeats;
 }
 
+// ReLU backward fused with the bias gradient: one pass over grad_out and y
+// (mlp_ops.hip).  Outputs and the fp32 partial slab come from the torch
+// allocator, so the op can be captured in a hipGraph.
+std::vector<torch::Tensor> relu_bwd_bias_grad(torch::Tensor grad_out,
+                                              torch::Tensor y) {
+  CHECK_CUDA(grad_out); CHECK_CUDA(y);
+  CHECK_CONTIG(grad_out); CHECK_CONTIG(y);
+  TORCH_CHECK(grad_out.dtype() == torch::kBFloat16 &&
+              y.dtype() == torch::kBFloat16, "bf16 required");
+  TORCH_CHECK(grad_out.dim() == 2 && grad_out.sizes() == y.sizes(),
+              "grad_out and y must be [B, N]");
+  const int64_t B = grad_out.size(0);
+  const int64_t N = grad_out.size(1);
+  TORCH_CHECK(N % 8 == 0 && N < (int64_t(1) << 31), "N % 8 == 0 required");
+  auto grad_in = torch::empty_like(grad_out);
+  if (B == 0 || N == 0) {
+    return {grad_in, torch::zeros({N}, grad_out.options())};
+  }
+  auto bias_grad = torch::empty({N}, grad_out.options());
+  int64_t rows_per_chunk = 0, num_chunks = 0;
+  relu_bwd_bias_grad_plan(B, (int)N, &rows_per_chunk, &num_chunks);
+  auto slab = torch::empty({num_chunks, N},
+                           grad_out.options().dtype(torch::kFloat32));
+  launch_relu_bwd_bias_grad(grad_out.data_ptr(), y.data_ptr(),
+                            grad_in.data_ptr(), slab.data_ptr<float>(),
+                            bias_grad.data_ptr(), B, (int)N, rows_per_chunk,
+                            num_chunks, current_stream());
+  return {grad_in, bias_grad};
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -510,4 +540,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "fused DLRM pairwise-dot interaction forward (MFMA bf16, gfx950)");
   m.def("dot_interact_bwd", &dot_interact_bwd,
         "fused DLRM pairwise-dot interaction backward (MFMA bf16, gfx950)");
+  m.def("relu_bwd_bias_grad", &relu_bwd_bias_grad,
+        "ReLU backward + bias gradient in one pass -> (grad_in, bias_grad) "
+        "(gfx950)");
 }

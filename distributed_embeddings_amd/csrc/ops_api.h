@@ -99,6 +99,16 @@ void launch_dot_interact_bwd(const void* gout, const void* feats, void* gfeats,
                              int64_t B, int F, int D, int out_w, int tri_n,
                              hipStream_t stream);
 
+// mlp_ops.hip.  relu_bwd_bias_grad: grad_in = (y <= 0) ? 0 : grad_out and
+// bias_grad = bf16(column sums of grad_in), bf16 [B, N] with N % 8 == 0.
+// The plan gives the slab shape [num_chunks, N] fp32 the launcher needs.
+void relu_bwd_bias_grad_plan(int64_t B, int N, int64_t* rows_per_chunk,
+                             int64_t* num_chunks);
+void launch_relu_bwd_bias_grad(const void* grad_out, const void* y,
+                               void* grad_in, float* slab, void* bias_grad,
+                               int64_t B, int N, int64_t rows_per_chunk,
+                               int64_t num_chunks, hipStream_t stream);
+
 size_t custom_radix_sort_hist_elems(int64_t n);
 
 void custom_radix_sort_keys(const uint64_t* keys_in, uint64_t* keys_out,

@@ -7,8 +7,9 @@ bottom MLP over dense features, per-category embedding tables behind
 interaction (lower triangle) re-concatenated with the bottom MLP output, and
 a top MLP producing one logit.
 
-MI355X notes: the MLPs run as plain ``nn.Linear`` (hipBLASLt GEMMs, TunableOp
-selections shipped in profiles/) under bf16 autocast; the pairwise-dot
+MI355X notes: the MLPs are ``ops.mlp.MLP`` stacks of ``nn.Linear`` (hipBLASLt
+GEMMs, TunableOp selections shipped in profiles/; under bf16 autocast the
+ReLU backward and the bias gradient run as one kernel); the pairwise-dot
 interaction runs as one fused MFMA kernel each direction
 (``csrc/dot_interact.hip``, dispatched by ``ops/dot_interact.py``; plain
 bmm fallback when the shape or dtype gate fails).
@@ -24,6 +25,7 @@ from torch import nn
 from ..layers.embedding import Embedding, scaled_uniform_init
 from ..ops.dot_interact import dot_interact as fused_dot_interact
 from ..ops.dot_interact import dot_interact_packed
+from ..ops.mlp import MLP
 from ..parallel import comm
 from ..parallel.dist_embedding import DistributedEmbedding
 
@@ -49,7 +51,7 @@ def dot_interact(emb_outs: List[torch.Tensor], bottom_mlp_out: torch.Tensor,
     return torch.cat(parts, dim=1)
 
 
-def _mlp(sizes: Sequence[int], in_dim: int, final_linear: bool) -> nn.Sequential:
+def _mlp(sizes: Sequence[int], in_dim: int, final_linear: bool) -> MLP:
     layers: List[nn.Module] = []
     d = in_dim
     for i, s in enumerate(sizes):
@@ -60,7 +62,7 @@ def _mlp(sizes: Sequence[int], in_dim: int, final_linear: bool) -> nn.Sequential
         if not (final_linear and i == len(sizes) - 1):
             layers.append(nn.ReLU(inplace=True))
         d = s
-    return nn.Sequential(*layers)
+    return MLP(*layers)
 
 
 class DLRM(nn.Module):

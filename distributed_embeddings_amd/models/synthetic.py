@@ -14,6 +14,7 @@ import torch
 from torch import nn
 
 from ..layers.embedding import Embedding
+from ..ops.mlp import MLP
 from ..parallel import comm
 from ..parallel.dist_embedding import DistributedEmbedding
 from .config import ModelConfig
@@ -83,7 +84,7 @@ class SyntheticModel(nn.Module):
             mods += [nn.Linear(d, s), nn.ReLU(inplace=True)]
             d = s
         mods.append(nn.Linear(d, 1))
-        self.mlp = nn.Sequential(*mods)
+        self.mlp = MLP(*mods)
 
     def forward(self, numerical: torch.Tensor, cat_features) -> torch.Tensor:
         # under autocast the MLP runs bf16: ask for bf16 embedding outputs
