@@ -298,6 +298,20 @@ void hash_rehash(torch::Tensor old_keys, torch::Tensor old_values,
                        current_stream());
 }
 
+// Adagrad state is fp32 [vocab, width]; a 1-D fp32 [vocab] state selects
+// row-wise Adagrad (one accumulator per row).  Returns true for row-wise.
+static bool check_adagrad_state(const torch::Tensor& state,
+                                const torch::Tensor& weight) {
+  CHECK_CUDA(state); CHECK_CONTIG(state);
+  const bool rowwise = state.dim() == 1 && state.size(0) == weight.size(0);
+  TORCH_CHECK(rowwise || state.sizes() == weight.sizes(),
+              "adagrad state shape mismatch: expected [vocab, width] "
+              "(element-wise) or [vocab] (row-wise), got ", state.sizes(),
+              " for weight ", weight.sizes());
+  TORCH_CHECK(state.dtype() == torch::kFloat32, "adagrad state must be fp32");
+  return rowwise;
+}
+
 void sparse_row_update(torch::Tensor weight, torch::Tensor state,
                        torch::Tensor ids, torch::Tensor grad, double lr,
                        double eps, bool adagrad) {
@@ -310,17 +324,16 @@ void sparse_row_update(torch::Tensor weight, torch::Tensor state,
   const int64_t n = ids.numel();
   if (n == 0) return;
   float* state_ptr = nullptr;
+  bool rowwise = false;
   if (adagrad) {
-    CHECK_CUDA(state); CHECK_CONTIG(state);
-    TORCH_CHECK(state.sizes() == weight.sizes(), "adagrad state shape mismatch");
-    TORCH_CHECK(state.dtype() == torch::kFloat32, "adagrad state must be fp32");
+    rowwise = check_adagrad_state(state, weight);
     state_ptr = state.data_ptr<float>();
   }
   launch_sparse_row_update(weight.data_ptr(),
                            weight.dtype() == torch::kBFloat16, state_ptr,
                            ids.data_ptr<int64_t>(), grad.data_ptr<float>(), n,
                            (int)weight.size(1), (float)lr, (float)eps, adagrad,
-                           current_stream());
+                           rowwise, current_stream());
 }
 
 void csr_fused_optimizer_apply(torch::Tensor weight, torch::Tensor state,
@@ -364,10 +377,9 @@ void csr_fused_optimizer_apply(torch::Tensor weight, torch::Tensor state,
   torch::Tensor scratch;
   float* scratch_ptr = nullptr;
   int64_t scratch_rows = 0;
+  bool rowwise = false;
   if (adagrad) {
-    CHECK_CUDA(state); CHECK_CONTIG(state);
-    TORCH_CHECK(state.sizes() == weight.sizes(), "adagrad state shape mismatch");
-    TORCH_CHECK(state.dtype() == torch::kFloat32, "adagrad state must be fp32");
+    rowwise = check_adagrad_state(state, weight);
     state_ptr = state.data_ptr<float>();
   }
   if (adagrad || wbf16) {
@@ -387,7 +399,7 @@ void csr_fused_optimizer_apply(torch::Tensor weight, torch::Tensor state,
                                  long_count.data_ptr<int32_t>(),
                                  work_items.data_ptr<int64_t>(),
                                  n_work.data_ptr<int32_t>(), scratch_ptr,
-                                 scratch_rows, adagrad, stream);
+                                 scratch_rows, adagrad, rowwise, stream);
 }
 
 torch::Tensor dot_interact_fwd(torch::Tensor feats, int64_t out_w) {
@@ -529,9 +541,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("integer_lookup", &integer_lookup,
         "open-addressing hash vocab build + lookup (gfx950)");
   m.def("sparse_row_update", &sparse_row_update,
-        "fused sparse SGD/Adagrad row update (gfx950)");
+        "fused sparse SGD/Adagrad/row-wise Adagrad row update (gfx950)");
   m.def("csr_fused_optimizer_apply", &csr_fused_optimizer_apply,
-        "in-backward fused SGD/Adagrad update (gfx950)");
+        "in-backward fused SGD/Adagrad/row-wise Adagrad update (gfx950)");
   m.def("dot_interact_fwd_packed", &dot_interact_fwd_packed,
         "pairwise-dot interaction on (bottom, packed, perm) (MFMA, gfx950)");
   m.def("dot_interact_bwd_packed", &dot_interact_bwd_packed,

@@ -17,8 +17,9 @@
 //     radix sort (hand-written, radix_sort.hip; rocPRIM via
 //     DE_USE_ROCPRIM_SORT=1) + head-flag scan unique + segmented sum reusing
 //     the forward kernels with per-id weights (K5-K7 equivalent).
-//   * csr_fused_optimizer_apply — the same pipeline with the SGD/Adagrad
-//     update applied in place (no host sync; hipGraph-capturable).
+//   * csr_fused_optimizer_apply — the same pipeline with the SGD, Adagrad or
+//     row-wise Adagrad update applied in place (no host sync;
+//     hipGraph-capturable).
 //   * integer_lookup      — open-addressing (linear probe) int64 hash
 //     resident in torch buffers; two-kernel design (free-slot scan, then
 //     insert_and_find with device-scope 64-bit atomicCAS) replacing the
@@ -234,6 +235,50 @@ __device__ __forceinline__ void apply_row_update(PT* w, float* state, float g,
   } else {
     pt_store(w, pt_load(w) - lr * g);
   }
+}
+
+// Row-wise Adagrad: one fp32 accumulator per row,
+//   s += mean_c(g[c]^2);  w[c] -= lr * g[c] / (sqrt(s) + eps).
+// The helpers below are the pieces its three kernels share.
+
+// Sum of v over the `tile` (pow2 <= WAVE) lanes of the caller's lane group.
+// The xor butterfly never leaves the group and every lane of the group ends
+// with the same bits, so every lane of the group has to call it.
+__device__ __forceinline__ float tile_sum(float v, int tile) {
+  for (int off = tile >> 1; off > 0; off >>= 1) v += __shfl_xor(v, off);
+  return v;
+}
+
+// Adds the group's mean square to state[0] and returns sqrt(new state) + eps
+// to every lane of the `tile`-lane group.  Only the group's first lane of a
+// `live` group touches memory; the others get the new value by shuffle, so
+// every lane of the group has to call this as well.
+__device__ __forceinline__ float rowwise_denom(float* state, float ssq,
+                                               int width, int lane, int tile,
+                                               bool live, float eps) {
+  const int leader = lane & ~(tile - 1);
+  float st = 0.f;
+  if (live && lane == leader) {
+    st = *state + ssq / (float)width;
+    *state = st;
+  }
+  st = __shfl(st, leader);
+  return sqrtf(st) + eps;
+}
+
+// One wave applies one row whose summed gradient g[0..width) sits in memory
+// nobody writes during the kernel (the optimizer step's grad rows, the
+// finalize kernel's completed scratch rows): squares first, update second.
+template <typename PT>
+__device__ __forceinline__ void rowwise_wave_update(
+    PT* __restrict__ w, float* __restrict__ state, const float* __restrict__ g,
+    int width, int lane, float lr, float eps) {
+  float ssq = 0.f;
+  for (int c = lane; c < width; c += WAVE) ssq += g[c] * g[c];
+  ssq = tile_sum(ssq, WAVE);
+  const float denom = rowwise_denom(state, ssq, width, lane, WAVE, true, eps);
+  for (int c = lane; c < width; c += WAVE)
+    pt_store(&w[c], pt_load(&w[c]) - lr * g[c] / denom);
 }
 
 // ---------------------------------------------------------------------------
@@ -879,6 +924,89 @@ __global__ void sorted_opt_update(PT* __restrict__ weight,
   }
 }
 
+// Row-wise Adagrad twin of sorted_opt_update.  A row's sum of squares has to
+// be complete before its first column moves, so the wide path walks the
+// columns twice: once for the squares, once for the update.  A row that fits
+// one column pass (width <= tile_w * VEC) keeps its sums in registers in
+// between; a wider one gathers them a second time.  The row loop and both
+// column loops have wave-uniform trip counts, and a wide group with nothing
+// to do stays in step with live == false, because the lanes of one wave
+// shuffle together.
+template <int TILE, int VEC, bool HAS_W, typename PT, typename GT>
+__global__ void sorted_opt_update_rowwise(
+    PT* __restrict__ weight, float* __restrict__ state, float eps,
+    const int64_t* __restrict__ sorted_ids, const int64_t* __restrict__ seg,
+    const int64_t* __restrict__ srow, const float* __restrict__ sw,
+    const GT* __restrict__ grad_out, const float* __restrict__ lr_ptr,
+    const int32_t* __restrict__ nu_ptr, int64_t long_thresh, int width,
+    int64_t* __restrict__ long_rows, int32_t* __restrict__ long_count,
+    int tile_w) {
+  const WaveCoord wc = wave_coord();
+  const TileCoord tc = tile_coord(wc.lane, TILE > 0 ? WAVE : tile_w);
+  const float lr = *lr_ptr;
+  const int64_t n_segs = *nu_ptr;
+  for (int64_t rbase = wc.wave_id * tc.rpw; rbase < n_segs;
+       rbase += wc.n_waves * tc.rpw) {
+    const int64_t r = rbase + tc.sub;
+    int64_t s = 0, e = 0;
+    if (r < n_segs) {
+      s = seg[r];
+      e = seg[r + 1];
+    }
+    bool live = s < e;
+    if (live && e - s > long_thresh) {
+      if (tc.tl == 0) long_rows[atomicAdd(long_count, 1)] = r;
+      live = false;
+    }
+    const int64_t uid = live ? sorted_ids[s] : 0;
+    PT* wrow = weight + uid * (int64_t)width;
+    if constexpr (TILE > 0) {
+      if (!live) continue;  // one segment per wave: the whole wave leaves
+      const float g = narrow_reduce<TILE, WAVE / TILE, 2, HAS_W, false>(
+          grad_out, srow, sw, 0, width, s, e, wc.lane);
+      // the fold leaves partial sums on lanes >= TILE: they count as 0
+      const bool mine = wc.lane < TILE && wc.lane < width;
+      const float ssq = tile_sum(mine ? g * g : 0.f, WAVE);
+      const float denom =
+          rowwise_denom(&state[uid], ssq, width, wc.lane, WAVE, true, eps);
+      if (mine)
+        pt_store(&wrow[wc.lane], pt_load(&wrow[wc.lane]) - lr * g / denom);
+    } else {
+      const int pass_w = tile_w * VEC;
+      const int n_pass = (width + pass_w - 1) / pass_w;
+      float acc[VEC];
+#pragma unroll
+      for (int v = 0; v < VEC; ++v) acc[v] = 0.f;
+      float ssq = 0.f;
+      for (int p = 0; p < n_pass; ++p) {
+        const int col0 = p * pass_w + tc.tl * VEC;
+        if (live && col0 < width) {
+          wide_accumulate<VEC, HAS_W, false>(grad_out, srow, sw, 0, width, col0,
+                                             s, e, acc);
+#pragma unroll
+          for (int v = 0; v < VEC; ++v) ssq += acc[v] * acc[v];
+        }
+      }
+      ssq = tile_sum(ssq, tile_w);
+      const float denom =
+          rowwise_denom(&state[uid], ssq, width, wc.lane, tile_w, live, eps);
+      for (int p = 0; p < n_pass; ++p) {
+        const int col0 = p * pass_w + tc.tl * VEC;
+        if (live && col0 < width) {
+          if (n_pass > 1)
+            wide_accumulate<VEC, HAS_W, false>(grad_out, srow, sw, 0, width,
+                                               col0, s, e, acc);
+          float wv[VEC];
+          pt_loadv<VEC>(wrow + col0, wv);
+#pragma unroll
+          for (int v = 0; v < VEC; ++v) wv[v] -= lr * acc[v] / denom;
+          pt_storev<VEC>(wrow + col0, wv);
+        }
+      }
+    }
+  }
+}
+
 // Long segments, fp32 SGD: chunk partials atomically into the weight
 // (linear).  Otherwise: chunk partials into fp32 scratch rows, then finalize.
 template <int TILE, int VEC, bool HAS_W, bool TO_SCRATCH, typename GT>
@@ -943,6 +1071,24 @@ __global__ void sorted_long_finalize(
   }
 }
 
+// Row-wise Adagrad finalize: the chunk kernel has completed the scratch row.
+template <typename PT>
+__global__ void sorted_long_finalize_rowwise(
+    PT* __restrict__ weight, float* __restrict__ state, float eps,
+    const int64_t* __restrict__ sorted_ids, const int64_t* __restrict__ seg,
+    const float* __restrict__ lr_ptr, int width,
+    const int64_t* __restrict__ long_rows,
+    const int32_t* __restrict__ long_count, const float* __restrict__ scratch) {
+  const WaveCoord wc = wave_coord();
+  const float lr = *lr_ptr;
+  const int64_t n_long = *long_count;
+  for (int64_t li = wc.wave_id; li < n_long; li += wc.n_waves) {
+    const int64_t uid = sorted_ids[seg[long_rows[li]]];
+    rowwise_wave_update(weight + uid * (int64_t)width, &state[uid],
+                        scratch + li * (int64_t)width, width, wc.lane, lr, eps);
+  }
+}
+
 template <typename PT, typename GT>
 static void launch_sorted_optimizer_update_t(
     PT* weight, float* state, float eps, const int64_t* sorted_ids,
@@ -950,7 +1096,7 @@ static void launch_sorted_optimizer_update_t(
     const GT* grad_out, const float* lr, const int32_t* nu_ptr,
     int64_t max_segs, int width, int64_t* long_rows, int32_t* long_count,
     int64_t* work_items, int32_t* n_work, float* long_scratch, bool adagrad,
-    hipStream_t stream) {
+    bool rowwise, hipStream_t stream) {
   const dim3 block(256);
   // bf16 weights have no atomicAdd: their long-SGD path also goes through the
   // fp32 scratch + finalize pair.
@@ -961,13 +1107,22 @@ static void launch_sorted_optimizer_update_t(
     const dim3 grid(pick_grid(t.row_waves, block.x / WAVE));
     dispatch_bool(sw != nullptr, [&](auto has_w_t) {
       constexpr bool HAS_W = decltype(has_w_t)::value;
-      dispatch_bool(adagrad, [&](auto ada) {
+      if (rowwise) {
         hipLaunchKernelGGL(
-            (sorted_opt_update<TILE, VEC, HAS_W, decltype(ada)::value, PT, GT>),
-            grid, block, 0, stream, weight, state, eps, sorted_ids, seg, srow,
-            sw, grad_out, lr, nu_ptr, (int64_t)LONG_T, width, long_rows,
-            long_count, t.tile_w);
-      });
+            (sorted_opt_update_rowwise<TILE, VEC, HAS_W, PT, GT>), grid, block,
+            0, stream, weight, state, eps, sorted_ids, seg, srow, sw, grad_out,
+            lr, nu_ptr, (int64_t)LONG_T, width, long_rows, long_count,
+            t.tile_w);
+      } else {
+        dispatch_bool(adagrad, [&](auto ada) {
+          hipLaunchKernelGGL(
+              (sorted_opt_update<TILE, VEC, HAS_W, decltype(ada)::value, PT,
+                                 GT>),
+              grid, block, 0, stream, weight, state, eps, sorted_ids, seg,
+              srow, sw, grad_out, lr, nu_ptr, (int64_t)LONG_T, width,
+              long_rows, long_count, t.tile_w);
+        });
+      }
       hipLaunchKernelGGL(expand_long_work, dim3(512), block, 0, stream,
                          long_rows, long_count, seg, work_items, n_work);
       dispatch_bool(use_scratch, [&](auto to_scratch) {
@@ -979,7 +1134,11 @@ static void launch_sorted_optimizer_update_t(
             work_items, n_work, t.tile_w);
       });
     });
-    if (use_scratch)
+    if (rowwise)
+      hipLaunchKernelGGL((sorted_long_finalize_rowwise<PT>), dim3(256), block,
+                         0, stream, weight, state, eps, sorted_ids, seg, lr,
+                         width, long_rows, long_count, long_scratch);
+    else if (use_scratch)
       dispatch_bool(adagrad, [&](auto ada) {
         hipLaunchKernelGGL((sorted_long_finalize<decltype(ada)::value, PT>),
                            dim3(256), block, 0, stream, weight, state, eps,
@@ -1000,7 +1159,8 @@ void launch_sorted_optimizer_update(void* weight, bool weight_bf16,
                                     int64_t* long_rows, int32_t* long_count,
                                     int64_t* work_items, int32_t* n_work,
                                     float* long_scratch, int64_t scratch_rows,
-                                    bool adagrad, hipStream_t stream) {
+                                    bool adagrad, bool rowwise,
+                                    hipStream_t stream) {
   hipMemsetAsync(long_count, 0, sizeof(int32_t), stream);
   hipMemsetAsync(n_work, 0, sizeof(int32_t), stream);
   if (long_scratch) {
@@ -1014,7 +1174,8 @@ void launch_sorted_optimizer_update(void* weight, bool weight_bf16,
       launch_sorted_optimizer_update_t(
           (PT*)weight, state, eps, sorted_ids, seg, srow, sw,
           (const GT*)grad_out, lr, nu_ptr, max_segs, width, long_rows,
-          long_count, work_items, n_work, long_scratch, adagrad, stream);
+          long_count, work_items, n_work, long_scratch, adagrad, rowwise,
+          stream);
     });
   });
 }
@@ -1043,15 +1204,37 @@ __global__ void sparse_row_update(PT* __restrict__ weight,
   }
 }
 
+// Row-wise Adagrad: state is [vocab], one float per row.
+template <typename PT>
+__global__ void sparse_row_update_rowwise(PT* __restrict__ weight,
+                                          float* __restrict__ state,
+                                          const int64_t* __restrict__ ids,
+                                          const float* __restrict__ grad,
+                                          int64_t num_rows, int width,
+                                          float lr, float eps) {
+  const WaveCoord wc = wave_coord();
+  for (int64_t r = wc.wave_id; r < num_rows; r += wc.n_waves) {
+    const int64_t uid = ids[r];
+    rowwise_wave_update(weight + uid * (int64_t)width, &state[uid],
+                        grad + r * (int64_t)width, width, wc.lane, lr, eps);
+  }
+}
+
 void launch_sparse_row_update(void* weight, bool weight_bf16, float* state,
                               const int64_t* ids, const float* grad,
                               int64_t num_rows, int width, float lr, float eps,
-                              bool adagrad, hipStream_t stream) {
+                              bool adagrad, bool rowwise, hipStream_t stream) {
   const int block = 256;
   const int grid = pick_grid(num_rows, block / WAVE);
   dispatch_bool(weight_bf16, [&](auto w_bf16) {
+    using PT = storage_t<decltype(w_bf16)>;
+    if (rowwise) {
+      hipLaunchKernelGGL((sparse_row_update_rowwise<PT>), dim3(grid),
+                         dim3(block), 0, stream, (PT*)weight, state, ids, grad,
+                         num_rows, width, lr, eps);
+      return;
+    }
     dispatch_bool(adagrad, [&](auto ada) {
-      using PT = storage_t<decltype(w_bf16)>;
       hipLaunchKernelGGL((sparse_row_update<decltype(ada)::value, PT>),
                          dim3(grid), dim3(block), 0, stream, (PT*)weight,
                          state, ids, grad, num_rows, width, lr, eps);

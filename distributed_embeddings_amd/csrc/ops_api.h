@@ -64,6 +64,8 @@ void launch_hash_reinsert(const int64_t* old_keys, const int64_t* old_vals,
 void launch_pad_seg_offsets(int64_t* seg, int64_t n, const int32_t* num_unique,
                             const int64_t* valid_end, hipStream_t stream);
 
+// rowwise (row-wise Adagrad) takes state as [vocab] fp32, one float per row,
+// in place of Adagrad's [vocab, width]; it implies adagrad.
 void launch_sorted_optimizer_update(void* weight, bool weight_bf16,
                                     float* state, float eps,
                                     const int64_t* sorted_ids,
@@ -75,12 +77,13 @@ void launch_sorted_optimizer_update(void* weight, bool weight_bf16,
                                     int64_t* long_rows, int32_t* long_count,
                                     int64_t* work_items, int32_t* n_work,
                                     float* long_scratch, int64_t scratch_rows,
-                                    bool adagrad, hipStream_t stream);
+                                    bool adagrad, bool rowwise,
+                                    hipStream_t stream);
 
 void launch_sparse_row_update(void* weight, bool weight_bf16, float* state,
                               const int64_t* ids, const float* grad,
                               int64_t num_rows, int width, float lr, float eps,
-                              bool adagrad, hipStream_t stream);
+                              bool adagrad, bool rowwise, hipStream_t stream);
 
 void launch_dot_interact_fwd_packed(const void* bottom, const void* packed,
                                     const int* perm, void* out, int64_t B,

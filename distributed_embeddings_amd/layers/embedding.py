@@ -98,10 +98,15 @@ class Embedding(nn.Module):
 
     def enable_fused_optimizer(self, method: str, lr: float, eps: float = 1e-10):
         """In-backward fused optimizer: the lookup's backward applies the
-        SGD/Adagrad update directly (no grad tensor, no host sync; the step
-        becomes hipGraph-capturable).  The training optimizer must not also
-        update this weight (its ``.grad`` stays ``None``)."""
-        if method not in ("sgd", "adagrad"):
+        update directly (no grad tensor, no host sync; the step becomes
+        hipGraph-capturable).  The training optimizer must not also update
+        this weight (its ``.grad`` stays ``None``).
+
+        ``method`` is ``"sgd"``, ``"adagrad"`` (fp32 state
+        ``[input_dim, output_dim]``) or ``"rowwise_adagrad"`` (fp32 state
+        ``[input_dim]``: one accumulator per row, fed with the mean square of
+        the row's summed gradient).  Calling it again replaces the state."""
+        if method not in ("sgd", "adagrad", "rowwise_adagrad"):
             raise ValueError(f"unknown fused optimizer {method!r}")
         for name in ("_fused_lr", "_fused_state"):  # allow re-configuring
             if name in self._buffers:
@@ -111,11 +116,12 @@ class Embedding(nn.Module):
                                           device=self.weight.device))
         self._fused_method = method
         self._fused_eps = float(eps)
-        if method == "adagrad":
+        if method in ("adagrad", "rowwise_adagrad"):
             # fp32 state regardless of table storage dtype
+            shape = (self.weight.shape if method == "adagrad"
+                     else self.weight.shape[:1])
             self.register_buffer("_fused_state",
-                                 torch.zeros(self.weight.shape,
-                                             dtype=torch.float32,
+                                 torch.zeros(shape, dtype=torch.float32,
                                              device=self.weight.device))
         else:
             self.register_buffer("_fused_state",
@@ -143,7 +149,7 @@ class Embedding(nn.Module):
         if getattr(self, "_fused_lr", None) is not None and self.training:
             return csr_lookup_fused_optimizer(
                 self.weight, values, row_splits, combiner, self._fused_lr,
-                self._fused_state, self._fused_method == "adagrad",
+                self._fused_state, self._fused_method != "sgd",
                 self._fused_eps, out_dtype)
         from ..ops.embedding_lookup import _CsrLookup
         return _CsrLookup.apply(self.weight, values, row_splits, combiner,

@@ -180,7 +180,9 @@ class _CsrLookupFusedOptimizer(torch.autograd.Function):
     host sync, and the whole training step becomes hipGraph-capturable.
     ``lr`` is a 1-element fp32 device tensor so schedules can update it
     without touching the graph; ``state`` is the Adagrad accumulator (empty
-    tensor for SGD).
+    tensor for SGD).  With ``adagrad`` set, a 1-D fp32 ``[vocab]`` state
+    selects row-wise Adagrad: ``state[r] += mean_c(G[r, c]^2)`` on the summed
+    row ``G[r]``, then ``w[r] -= lr * G[r] / (sqrt(state[r]) + eps)``.
     """
 
     @staticmethod
@@ -212,8 +214,13 @@ class _CsrLookupFusedOptimizer(torch.autograd.Function):
                     ctx.combiner)
                 lr_v = lr.item()
                 if ctx.adagrad:
-                    state.index_add_(0, unique_ids, unique_grad * unique_grad)
+                    sq = unique_grad * unique_grad
+                    rowwise = state.dim() == 1
+                    state.index_add_(0, unique_ids,
+                                     sq.mean(dim=1) if rowwise else sq)
                     denom = state.index_select(0, unique_ids).sqrt_().add_(ctx.eps)
+                    if rowwise:
+                        denom = denom.unsqueeze(1)
                     weight.index_add_(
                         0, unique_ids,
                         (-lr_v * unique_grad / denom).to(weight.dtype))

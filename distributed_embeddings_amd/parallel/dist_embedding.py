@@ -241,11 +241,19 @@ class DistributedEmbedding(nn.Module):
         return self.enable_fused_optimizer("sgd", lr)
 
     def enable_fused_optimizer(self, method: str, lr: float, eps: float = 1e-10):
-        """Enables in-backward fused SGD/Adagrad on all model-parallel tables
-        (col + row groups).  Data-parallel tables keep sparse grads (they
-        need the allreduce); CPU-offloaded tables keep sparse grads too (their
-        lookup runs through the CPU fallback, not the HIP fused kernel).
-        See Embedding.enable_fused_optimizer."""
+        """Enables the in-backward fused optimizer (``"sgd"``, ``"adagrad"``
+        or ``"rowwise_adagrad"``) on all model-parallel tables (col + row
+        groups).  Data-parallel tables keep sparse grads (they need the
+        allreduce); CPU-offloaded tables keep sparse grads too (their lookup
+        runs through the CPU fallback, not the HIP fused kernel).
+        See Embedding.enable_fused_optimizer.
+
+        Row-wise Adagrad state is shard-local.  A row-sliced shard owns whole
+        rows, so its state equals the undistributed table's.  A column-sliced
+        shard sees only its own columns and takes the row mean over that
+        slice, so a column-sliced table does *not* train like the unsliced
+        one: each slice has its own per-row step size (TorchRec's column-wise
+        sharding behaves the same way).  The row sums are not all-reduced."""
         for lyr in list(self.col_layers) + list(self.row_layers):
             if getattr(lyr, "_cpu_offload", False):
                 continue

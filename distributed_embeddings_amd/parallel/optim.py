@@ -19,12 +19,15 @@ from ..ops import _backend
 
 
 class SparseEmbeddingOptimizer(torch.optim.Optimizer):
-    """SGD / Adagrad with fused sparse row updates.
+    """SGD / Adagrad / row-wise Adagrad with fused sparse row updates.
 
     Args:
       params: iterable of parameters (dense and sparse-grad mixed).
       lr: learning rate.
-      method: ``"sgd"`` or ``"adagrad"``.
+      method: ``"sgd"``, ``"adagrad"`` or ``"rowwise_adagrad"``.  Row-wise
+        Adagrad keeps one fp32 accumulator per row of a sparse-grad param
+        (state ``[vocab]``), fed with the mean square of the row's gradient.
+        Dense-grad params in the same optimizer keep element-wise Adagrad.
       eps: adagrad epsilon.
       assume_coalesced: trust that every sparse grad holds unique, sorted ids
         (true when each embedding parameter receives exactly one lookup
@@ -35,7 +38,7 @@ class SparseEmbeddingOptimizer(torch.optim.Optimizer):
 
     def __init__(self, params, lr: float = 0.01, method: str = "sgd",
                  eps: float = 1e-10, assume_coalesced: bool = True):
-        if method not in ("sgd", "adagrad"):
+        if method not in ("sgd", "adagrad", "rowwise_adagrad"):
             raise ValueError(f"unknown method {method!r}")
         defaults = dict(lr=lr, method=method, eps=eps,
                         assume_coalesced=assume_coalesced)
@@ -50,14 +53,15 @@ class SparseEmbeddingOptimizer(torch.optim.Optimizer):
         for group in self.param_groups:
             lr = group["lr"]
             eps = group["eps"]
-            adagrad = group["method"] == "adagrad"
+            adagrad = group["method"] != "sgd"
+            rowwise = group["method"] == "rowwise_adagrad"
             dense = []
             for p in group["params"]:
                 g = p.grad
                 if g is None:
                     continue
                 if g.layout == torch.sparse_coo:
-                    self._sparse_update(p, g, lr, eps, adagrad,
+                    self._sparse_update(p, g, lr, eps, adagrad, rowwise,
                                         group["assume_coalesced"])
                 else:
                     dense.append(p)
@@ -65,29 +69,35 @@ class SparseEmbeddingOptimizer(torch.optim.Optimizer):
                 self._dense_update_batch(dense, lr, eps, adagrad)
         return loss
 
-    def _state_for(self, p):
+    def _state_for(self, p, rowwise=False):
         st = self.state[p]
         if "sum" not in st:
             # fp32 accumulator state regardless of param storage dtype
-            st["sum"] = torch.zeros(p.shape, dtype=torch.float32,
-                                    device=p.device)
+            st["sum"] = torch.zeros(p.shape[:1] if rowwise else p.shape,
+                                    dtype=torch.float32, device=p.device)
         return st["sum"]
 
-    def _sparse_update(self, p, g, lr, eps, adagrad, assume_coalesced):
+    def _sparse_update(self, p, g, lr, eps, adagrad, rowwise,
+                       assume_coalesced):
         if not (assume_coalesced or g.is_coalesced()):
             g = g.coalesce()
         ids = g._indices()[0]
         vals = g._values().float()
         if p.is_cuda:
-            state = self._state_for(p) if adagrad else torch.empty(0)
+            # the kernel reads the mode off the state: [vocab] is row-wise
+            state = (self._state_for(p, rowwise) if adagrad
+                     else torch.empty(0))
             _backend.ops().sparse_row_update(p.data, state, ids.contiguous(),
                                              vals.contiguous(), lr, eps,
                                              adagrad)
         else:
             if adagrad:
-                state = self._state_for(p)
-                state.index_add_(0, ids, vals * vals)
+                state = self._state_for(p, rowwise)
+                sq = vals * vals
+                state.index_add_(0, ids, sq.mean(dim=1) if rowwise else sq)
                 denom = state.index_select(0, ids).sqrt_().add_(eps)
+                if rowwise:
+                    denom = denom.unsqueeze(1)
                 p.data.index_add_(0, ids, (-lr * vals / denom).to(p.dtype))
             else:
                 p.data.index_add_(0, ids, (-lr * vals).to(p.dtype))

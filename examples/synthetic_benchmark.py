@@ -37,7 +37,7 @@ def parse_args():
     p.add_argument("--alpha", type=float, default=1.05)
     p.add_argument("--column-slice-threshold", type=int, default=None)
     p.add_argument("--dp-input", action="store_true", default=True)
-    p.add_argument("--optimizer", default="adagrad", choices=["adagrad", "sgd"])
+    p.add_argument("--optimizer", default="adagrad", choices=["adagrad", "rowwise_adagrad", "sgd"])
     p.add_argument("--pool", type=int, default=4)
     p.add_argument("--graph", dest="graph", action="store_true", default=True,
                    help="hipGraph-capture the step (world==1; eager fallback)")
