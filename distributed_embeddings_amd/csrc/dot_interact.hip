@@ -197,10 +197,13 @@ __global__ void dot_interact_bwd(const __hip_bfloat16* __restrict__ gout,
 // its [F, D] grad in LDS (overwriting nothing the MFMA still needs) and
 // writes it back cooperatively the same way.
 
-// waves (= samples) per block: templated; DI_WPB is the measured default,
-// DE_DI_WPB env selects 2/4/8 for measurement (tools/bench_interact.py)
-// measured per-direction optima (tools/bench_interact.py sweep): fwd 2,
-// bwd 8 — the deltas are small; DE_DI_WPB overrides both for measurement
+// waves (= samples) per block: templated; DI_WPB_FWD / DI_WPB_BWD are the
+// measured defaults (tools/bench_interact.py sweep with the fixed-width
+// kernels below, profiles/interact_latency.md); DE_DI_WPB env selects 2/4/8
+// for both directions, for measurement.  The first two kernels take a
+// run-time D and serve the widths that have no fixed-width instance.
+#define DI_WPB_FWD 4
+#define DI_WPB_BWD 4
 static int di_wpb(int dflt) {
   static int v = [] {
     const char* e = getenv("DE_DI_WPB");
@@ -212,7 +215,7 @@ static int di_wpb(int dflt) {
 }
 
 template <int FMAX, int WPB>
-__global__ void dot_interact_fwd_packed(
+__global__ void dot_interact_fwd_packed_rt(
     const __hip_bfloat16* __restrict__ bottom,
     const __hip_bfloat16* __restrict__ packed,
     const int* __restrict__ perm, __hip_bfloat16* __restrict__ out, int64_t B,
@@ -291,7 +294,7 @@ __global__ void dot_interact_fwd_packed(
 }
 
 template <int FMAX, int WPB>
-__global__ void dot_interact_bwd_packed(
+__global__ void dot_interact_bwd_packed_rt(
     const __hip_bfloat16* __restrict__ gout,
     const __hip_bfloat16* __restrict__ bottom,
     const __hip_bfloat16* __restrict__ packed, const int* __restrict__ perm,
@@ -408,23 +411,429 @@ __global__ void dot_interact_bwd_packed(
   }
 }
 
+// ---------------------------------------------------------------------------
+// Packed kernels with a compile-time width (D = 32, 64, 128, 256); every
+// other D % 32 == 0 takes the run-time-D kernels above.
+//
+// What the fixed width buys (gfx950 assembly, profiles/interact_latency.md):
+//  - chunk -> (row, sample, col) is shifts and masks, and (sample, col) do not
+//    depend on the pass, so a thread computes them once;
+//  - perm is read once per thread, before the first feature load, and kept
+//    in registers as the row's element offset, for the load and the
+//    write-back alike;
+//  - the cooperative loops are fully unrolled with all global loads of a
+//    sample group issued before the first LDS write (D/16 x 16 B per thread
+//    in flight), and the write-back reads LDS the same way ahead of its
+//    stores.
+//
+// Chunk mapping, thread tid, pass it (D8 = D/8 chunks per row):
+//   row = it * (64 / D8) + tid / (WPB * D8)
+//   w   = (tid / D8) % WPB          sample within the block
+//   col = (tid % D8) * 8
+// so per row the WPB samples' segments are still contiguous (feature-major).
+//
+// The rows of out / gout start at b * out_w elements, which is 2-byte
+// aligned and no more (out_w = 479 without padding at the bench's F and D);
+// they are moved as 16-B vectors through a 2-byte-aligned type.
+// ---------------------------------------------------------------------------
+
+typedef __attribute__((ext_vector_type(4))) short bf16x4;
+typedef bf16x8 __attribute__((aligned(2))) bf16x8_u;
+typedef short v4i16_t __attribute__((vector_size(8)));
+typedef __attribute__((address_space(3))) v4i16_t lds_v4i16_t;
+
+// LDS writes of one lane read back by another lane of the same wave: the LDS
+// executes a wave's operations in order, this keeps the compiler from moving
+// them across.
+__device__ __forceinline__ void wave_lds_fence() {
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+}
+
+__device__ __forceinline__ short f32_to_bf16_bits(float v) {
+  __hip_bfloat16 hb(v);
+  return *reinterpret_cast<short*>(&hb);
+}
+
+__device__ __forceinline__ float bf16_bits_to_f32(short s) {
+  return __builtin_bit_cast(float, (unsigned)(unsigned short)s << 16);
+}
+
+// Backward LDS image: plain D-element rows whose 16-B chunks are XORed with
+// a function of the row, so that the 16 rows of an MFMA tile put one column
+// chunk on 16 different bank groups.  Without it every row of a 256-B-stride
+// image starts on bank 0: the transposed reads (8 rows per 32-lane half) and
+// the 8-B result stores (16 rows) serialize.  Element offset of (row, col):
+template <int D>
+__device__ __forceinline__ int swz(int row, int col) {
+  const int sw = (((row & 3) << 2) | ((row >> 2) & 3)) & (D / 8 - 1);
+  return row * D + ((((col >> 3) ^ sw) << 3) | (col & 7));
+}
+
+template <int D, int WPB>
+struct PackedIO {
+  static constexpr int D8 = D / 8;
+  static constexpr int RPI = WAVE / D8;  // rows per pass
+  static constexpr int NIT = 32 / RPI;   // passes = 16-B chunks per thread
+  int r0, w, col;
+  int64_t b;         // this thread's sample
+  int64_t off[NIT];  // element offset of its chunk of pass `it` in bottom
+                     // (row 0) or packed: the load and the write-back share it
+
+  __device__ __forceinline__ PackedIO(const int* __restrict__ perm, int F,
+                                      int64_t b0, int64_t sb, int64_t sp) {
+    const int tid = threadIdx.x;
+    r0 = tid / (WPB * D8);
+    w = (tid / D8) % WPB;
+    col = (tid % D8) * 8;
+    b = b0 + w;
+    int prow[NIT];
+#pragma unroll
+    for (int it = 0; it < NIT; ++it) {
+      // clamped index, not a branch: the NIT loads go out together.
+      // F >= 2: the launcher sees to it
+      const int row = it * RPI + r0;
+      const int pi = row < 1 ? 0 : (row < F ? row - 1 : F - 2);
+      prow[it] = perm[pi];
+    }
+#pragma unroll
+    for (int it = 0; it < NIT; ++it) {
+      // rows >= F are never addressed
+      const int row = it * RPI + r0;
+      off[it] = row == 0 ? b * D + col
+                         : (prow[it] * sp + b * sb) * (int64_t)D + col;
+    }
+    // perm is consumed here, in one wait, ahead of every predicated load: a
+    // wait placed among those has to assume that none of them was issued and
+    // so waits for all of them.  The empty asm pins the offsets to this point.
+#pragma unroll
+    for (int it = 0; it < NIT; ++it) asm volatile("" : "+v"(off[it]));
+  }
+
+  // global -> LDS image [w][32][LD] (+ PER_WAVE between samples), rows >= F
+  // and samples >= B zero-filled
+  template <int LD, int PER_WAVE, bool SWZ>
+  __device__ __forceinline__ void load(const short* __restrict__ bottom,
+                                       const short* __restrict__ packed,
+                                       short* lds_all, int64_t B, int F) const {
+    bf16x8 v[NIT];
+#pragma unroll
+    for (int it = 0; it < NIT; ++it) {
+      const int row = it * RPI + r0;
+      const bf16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
+      v[it] = z;
+      if (b < B && row < F) {
+        v[it] = *reinterpret_cast<const bf16x8*>(
+            (row == 0 ? bottom : packed) + off[it]);
+      }
+    }
+#pragma unroll
+    for (int it = 0; it < NIT; ++it) {
+      const int row = it * RPI + r0;
+      const int at_lds = SWZ ? swz<D>(row, col) : row * LD + col;
+      *reinterpret_cast<bf16x8*>(&lds_all[w * PER_WAVE + at_lds]) = v[it];
+    }
+  }
+};
+
+template <int D, int WPB>
+__global__ __launch_bounds__(WPB* WAVE) void dot_interact_fwd_packed(
+    const __hip_bfloat16* __restrict__ bottom,
+    const __hip_bfloat16* __restrict__ packed,
+    const int* __restrict__ perm, __hip_bfloat16* __restrict__ out, int64_t B,
+    int F, int out_w, int tri_n, int64_t sb, int64_t sp) {
+  extern __shared__ short lds_all[];
+  constexpr int LD = D + 8;  // +16 B row pad, as the unpacked forward
+  constexpr int PER_WAVE = 32 * LD;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int lane = threadIdx.x & (WAVE - 1);
+  short* lds = lds_all + wave * PER_WAVE;
+  // one block, one group of WPB samples: with a grid-stride loop here the
+  // compiler hoists every LDS address out of it and runs out of registers
+  const int64_t b0 = (int64_t)blockIdx.x * WPB;
+  const PackedIO<D, WPB> io(perm, F, b0, sb, sp);
+  {
+    io.template load<LD, PER_WAVE, false>(
+        reinterpret_cast<const short*>(bottom),
+        reinterpret_cast<const short*>(packed), lds_all, B, F);
+    __syncthreads();
+
+    const int64_t b = b0 + wave;
+    if (b < B) {
+      const int r16 = lane & 15;
+      const int khalf = lane >> 4;
+      const int tiles_mi[3] = {0, 1, 1};
+      const int tiles_ni[3] = {0, 0, 1};
+      f32x4 accs[3];
+#pragma unroll
+      for (int t = 0; t < 3; ++t) {
+        const int mi = tiles_mi[t], ni = tiles_ni[t];
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int k0 = 0; k0 < D; k0 += 32) {
+          bf16x8 a = *reinterpret_cast<const bf16x8*>(
+              &lds[(mi * 16 + r16) * LD + k0 + khalf * 8]);
+          bf16x8 bfr = *reinterpret_cast<const bf16x8*>(
+              &lds[(ni * 16 + r16) * LD + k0 + khalf * 8]);
+          acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, bfr, acc, 0, 0, 0);
+        }
+        accs[t] = acc;
+      }
+      // Rows 1.. of the tile are dead once all three products are in
+      // registers: the output row [tril | bottom | 0 up to a multiple of 8]
+      // is assembled there (<= 496 + D + 7 of the 31 * LD elements) and
+      // leaves as 16-B vectors.  Row 0 (bottom) stays where it is.
+      wave_lds_fence();
+      short* stage = lds + LD;
+#pragma unroll
+      for (int t = 0; t < 3; ++t) {
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) {
+          const int i = tiles_mi[t] * 16 + khalf * 4 + reg;
+          const int j = tiles_ni[t] * 16 + r16;
+          if (i > j && i < F) {
+            stage[i * (i - 1) / 2 + j] = f32_to_bf16_bits(accs[t][reg]);
+          }
+        }
+      }
+#pragma unroll
+      for (int c = lane; c < D; c += WAVE) stage[tri_n + c] = lds[c];
+      const int width = tri_n + D;
+      const int width8 = (width + 7) & ~7;
+      if (width + lane < width8) stage[width + lane] = 0;
+      wave_lds_fence();
+
+      short* orow = reinterpret_cast<short*>(out) + b * (int64_t)out_w;
+      const int nfull = out_w >> 3;  // whole 16-B chunks of the row
+      for (int c = lane; c < nfull; c += WAVE) {
+        bf16x8 v = {0, 0, 0, 0, 0, 0, 0, 0};
+        if (c * 8 < width8) v = *reinterpret_cast<const bf16x8*>(&stage[c * 8]);
+        *reinterpret_cast<bf16x8_u*>(&orow[c * 8]) = v;
+      }
+      const int e = nfull * 8 + lane;  // the row's last out_w % 8 elements
+      if (e < out_w) orow[e] = e < width ? stage[e] : (short)0;
+    }
+    __syncthreads();
+  }
+}
+
+// Backward, transposed product: gfeats^T[d][i] = sum_k X[k][d] * G[k][i].
+//  - A operand X^T: ds_read_b64_tr_b16 of the [32][D] image (swz above).  The
+//    16-lane group g takes rows 8g..8g+3 and 8g+4..8g+7 of columns
+//    d0..d0+15; lane 4q+p of the group supplies row q, columns 4p..4p+3.
+//    EXEC is all ones: the only branch around it is on the wave's own
+//    sample index, held in an SGPR.  The two groups of a 32-lane half read
+//    blocks 8 rows apart in the same columns: 32 distinct 8-B slots.
+//  - B operand G[k][i] = G[i][k] (symmetric): 8 consecutive k of row i,
+//    the same for every d0, so both 16-feature fragments are built once per
+//    sample and kept in registers.
+//  - C: lane holds d = d0 + 4*(lane>>4) + reg of feature i = lane & 15: one
+//    8-B LDS store per tile.
+// The sample's gout row comes in with 16-B loads into the 2 KB that held
+// G_sym: tril chunks at [0, 496) (a chunk may run up to 7 elements into the
+// bottom part, never past the row: D >= 32), the bottom part again at
+// [1024 - D, 1024) so that it is 8-B aligned for the C-operand read.
+// LDS per wave stays 32*D + 1024 elements.
+template <int D, int WPB>
+__global__ __launch_bounds__(WPB* WAVE, D >= 256 ? 2 : 4) void
+dot_interact_bwd_packed(
+    const __hip_bfloat16* __restrict__ gout,
+    const __hip_bfloat16* __restrict__ bottom,
+    const __hip_bfloat16* __restrict__ packed, const int* __restrict__ perm,
+    __hip_bfloat16* __restrict__ gbottom, __hip_bfloat16* __restrict__ gpacked,
+    int64_t B, int F, int out_w, int tri_n, int64_t sb, int64_t sp) {
+  static_assert(496 + 7 + D <= 1024, "gout row staging needs D <= 256");
+  extern __shared__ short lds_all[];
+  constexpr int PER_WAVE = 32 * D + 1024;
+  constexpr int D8 = D / 8;
+  constexpr int NJ = D / 16;
+  using IO = PackedIO<D, WPB>;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int lane = threadIdx.x & (WAVE - 1);
+  short* lds = lds_all + wave * PER_WAVE;
+  short* stage = lds + 32 * D;
+  short* gb = stage + 1024 - D;
+  // one block, one group of WPB samples (see the forward)
+  const int64_t b0 = (int64_t)blockIdx.x * WPB;
+  const IO io(perm, F, b0, sb, sp);
+  {
+    // the sample's gout row goes out ahead of the feature loads
+    const int64_t b = b0 + wave;
+    const bf16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
+    bf16x8 vt = z, vb = z;
+    if (b < B) {
+      const short* grow = reinterpret_cast<const short*>(gout) +
+                          b * (int64_t)out_w;
+      if (lane * 8 < tri_n) {
+        vt = *reinterpret_cast<const bf16x8_u*>(&grow[lane * 8]);
+      }
+      if (lane < D8) {
+        vb = *reinterpret_cast<const bf16x8_u*>(&grow[tri_n + lane * 8]);
+      }
+    }
+    io.template load<D, PER_WAVE, true>(
+        reinterpret_cast<const short*>(bottom),
+        reinterpret_cast<const short*>(packed), lds_all, B, F);
+    if (b < B) {
+      if (lane * 8 < tri_n) *reinterpret_cast<bf16x8*>(&stage[lane * 8]) = vt;
+      if (lane < D8) *reinterpret_cast<bf16x8*>(&gb[lane * 8]) = vb;
+    }
+    __syncthreads();
+
+    if (b < B) {
+      const int r16 = lane & 15;
+      const int khalf = lane >> 4;
+      bf16x8 g[2];
+#pragma unroll
+      for (int ni = 0; ni < 2; ++ni) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const int i = ni * 16 + r16, k = khalf * 8 + j;
+          const bool ok = i < F && k < F && i != k;
+          const int r = i > k ? i : k, c = i > k ? k : i;
+          const short s = stage[ok ? r * (r - 1) / 2 + c : 0];
+          g[ni][j] = ok ? s : (short)0;
+        }
+      }
+      const int xrow = khalf * 8 + (r16 >> 2), xcol = (lane & 3) * 4;
+      // NJB column tiles at a time: their X^T operands are all read before
+      // the first of their results is stored, and a result only overwrites
+      // columns that no later tile reads, so the gradient replaces the
+      // features in place
+      constexpr int NJB = NJ < 4 ? NJ : 4;
+#pragma unroll
+      for (int nj0 = 0; nj0 < NJ; nj0 += NJB) {
+        bf16x8 a[NJB];
+        bf16x4 gbv[NJB];
+#pragma unroll
+        for (int t = 0; t < NJB; ++t) {
+          const int d0 = (nj0 + t) * 16;
+          const v4i16_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+              (lds_v4i16_t*)(lds + swz<D>(xrow, d0 + xcol)));
+          const v4i16_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+              (lds_v4i16_t*)(lds + swz<D>(xrow + 4, d0 + xcol)));
+          a[t] = bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+          gbv[t] = *reinterpret_cast<const bf16x4*>(&gb[d0 + khalf * 4]);
+        }
+        wave_lds_fence();
+#pragma unroll
+        for (int t = 0; t < NJB; ++t) {
+          const int d0 = (nj0 + t) * 16;
+          // bottom-concat gradient of feature 0: the C operand of its column
+          f32x4 c0 = {0.f, 0.f, 0.f, 0.f};
+          if (r16 == 0) {
+#pragma unroll
+            for (int reg = 0; reg < 4; ++reg) {
+              c0[reg] = bf16_bits_to_f32(gbv[t][reg]);
+            }
+          }
+          const f32x4 zc = {0.f, 0.f, 0.f, 0.f};
+          const f32x4 acc0 =
+              __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[t], g[0], c0, 0, 0, 0);
+          const f32x4 acc1 =
+              __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[t], g[1], zc, 0, 0, 0);
+          const bf16x4 o0 = {
+              f32_to_bf16_bits(acc0[0]), f32_to_bf16_bits(acc0[1]),
+              f32_to_bf16_bits(acc0[2]), f32_to_bf16_bits(acc0[3])};
+          const bf16x4 o1 = {
+              f32_to_bf16_bits(acc1[0]), f32_to_bf16_bits(acc1[1]),
+              f32_to_bf16_bits(acc1[2]), f32_to_bf16_bits(acc1[3])};
+          *reinterpret_cast<bf16x4*>(&lds[swz<D>(r16, d0 + khalf * 4)]) = o0;
+          *reinterpret_cast<bf16x4*>(
+              &lds[swz<D>(16 + r16, d0 + khalf * 4)]) = o1;
+        }
+        wave_lds_fence();
+      }
+    }
+    __syncthreads();
+
+    // cooperative write-back: the load's mapping, LDS reads ahead of stores
+    {
+      const int64_t bw = io.b;
+      bf16x8 v[IO::NIT];
+#pragma unroll
+      for (int it = 0; it < IO::NIT; ++it) {
+        const int row = it * IO::RPI + io.r0;
+        v[it] = *reinterpret_cast<const bf16x8*>(
+            &lds_all[io.w * PER_WAVE + swz<D>(row, io.col)]);
+      }
+#pragma unroll
+      for (int it = 0; it < IO::NIT; ++it) {
+        const int row = it * IO::RPI + io.r0;
+        if (bw < B && row < F) {
+          short* dst = reinterpret_cast<short*>(row == 0 ? gbottom : gpacked);
+          *reinterpret_cast<bf16x8*>(dst + io.off[it]) = v[it];
+        }
+      }
+    }
+    __syncthreads();
+  }
+}
+
+#define DI_FOR_WPB(M) \
+  if (wpb == 2) { M(2); } else if (wpb == 8) { M(8); } else { M(4); }
+
+template <int D>
+static void launch_fwd_packed_d(const void* bottom, const void* packed,
+                                const int* perm, void* out, int64_t B, int F,
+                                int out_w, int tri_n, int64_t sb, int64_t sp,
+                                int wpb, int blocks, hipStream_t stream) {
+  const size_t lds = (size_t)wpb * 32 * (D + 8) * sizeof(short);
+#define LFWD(W)                                                                \
+  hipLaunchKernelGGL((dot_interact_fwd_packed<D, W>), dim3(blocks),            \
+                     dim3(W * WAVE), lds, stream,                              \
+                     (const __hip_bfloat16*)bottom,                            \
+                     (const __hip_bfloat16*)packed, perm, (__hip_bfloat16*)out,\
+                     B, F, out_w, tri_n, sb, sp)
+  DI_FOR_WPB(LFWD)
+#undef LFWD
+}
+
+template <int D>
+static void launch_bwd_packed_d(const void* gout, const void* bottom,
+                                const void* packed, const int* perm,
+                                void* gbottom, void* gpacked, int64_t B, int F,
+                                int out_w, int tri_n, int64_t sb, int64_t sp,
+                                int wpb, int blocks, hipStream_t stream) {
+  const size_t lds = (size_t)wpb * (32 * D + 32 * 32) * sizeof(short);
+#define LBWD(W)                                                                \
+  hipLaunchKernelGGL((dot_interact_bwd_packed<D, W>), dim3(blocks),            \
+                     dim3(W * WAVE), lds, stream, (const __hip_bfloat16*)gout, \
+                     (const __hip_bfloat16*)bottom,                            \
+                     (const __hip_bfloat16*)packed, perm,                      \
+                     (__hip_bfloat16*)gbottom, (__hip_bfloat16*)gpacked, B, F, \
+                     out_w, tri_n, sb, sp)
+  DI_FOR_WPB(LBWD)
+#undef LBWD
+}
+
 void launch_dot_interact_fwd_packed(const void* bottom, const void* packed,
                                     const int* perm, void* out, int64_t B,
                                     int F, int D, int out_w, int tri_n,
                                     int64_t sb, int64_t sp,
                                     hipStream_t stream) {
-  const int wpb = di_wpb(2);
-  const int block = wpb * WAVE;
-  int64_t blocks = (B + wpb - 1) / wpb;
-  if (blocks > 32768) blocks = 32768;
+  const int wpb = di_wpb(DI_WPB_FWD);
+  const int64_t groups = (B + wpb - 1) / wpb;
+  // one block per sample group, and perm is read unconditionally
+  const bool fixed_ok = groups <= INT32_MAX && F >= 2;
+  int blocks = (int)groups;
+#define LFWD_D(DD)                                                             \
+  launch_fwd_packed_d<DD>(bottom, packed, perm, out, B, F, out_w, tri_n, sb,   \
+                          sp, wpb, blocks, stream)
+  if (fixed_ok && D == 128) { LFWD_D(128); return; }
+  if (fixed_ok && D == 64) { LFWD_D(64); return; }
+  if (fixed_ok && D == 32) { LFWD_D(32); return; }
+  if (fixed_ok && D == 256) { LFWD_D(256); return; }
+#undef LFWD_D
+  if (groups > 32768) blocks = 32768;  // grid-stride kernels
   const size_t lds = (size_t)wpb * 32 * (D + 8) * sizeof(short);
 #define LFWD(W)                                                                \
-  hipLaunchKernelGGL((dot_interact_fwd_packed<32, W>), dim3((int)blocks),      \
-                     dim3(block), lds, stream,                                 \
+  hipLaunchKernelGGL((dot_interact_fwd_packed_rt<32, W>), dim3(blocks),        \
+                     dim3(W * WAVE), lds, stream,                              \
                      (const __hip_bfloat16*)bottom,                            \
                      (const __hip_bfloat16*)packed, perm, (__hip_bfloat16*)out,\
                      B, F, D, out_w, tri_n, sb, sp)
-  if (wpb == 2) LFWD(2); else if (wpb == 8) LFWD(8); else LFWD(4);
+  DI_FOR_WPB(LFWD)
 #undef LFWD
 }
 
@@ -434,21 +843,32 @@ void launch_dot_interact_bwd_packed(const void* gout, const void* bottom,
                                     int F, int D, int out_w, int tri_n,
                                     int64_t sb, int64_t sp,
                                     hipStream_t stream) {
-  const int wpb = di_wpb(8);
-  const int block = wpb * WAVE;
-  int64_t blocks = (B + wpb - 1) / wpb;
-  if (blocks > 32768) blocks = 32768;
+  const int wpb = di_wpb(DI_WPB_BWD);
+  const int64_t groups = (B + wpb - 1) / wpb;
+  // one block per sample group, and perm is read unconditionally
+  const bool fixed_ok = groups <= INT32_MAX && F >= 2;
+  int blocks = (int)groups;
+#define LBWD_D(DD)                                                             \
+  launch_bwd_packed_d<DD>(gout, bottom, packed, perm, gbottom, gpacked, B, F,  \
+                          out_w, tri_n, sb, sp, wpb, blocks, stream)
+  if (fixed_ok && D == 128) { LBWD_D(128); return; }
+  if (fixed_ok && D == 64) { LBWD_D(64); return; }
+  if (fixed_ok && D == 32) { LBWD_D(32); return; }
+  if (fixed_ok && D == 256) { LBWD_D(256); return; }
+#undef LBWD_D
+  if (groups > 32768) blocks = 32768;  // grid-stride kernels
   const size_t lds = (size_t)wpb * (32 * D + 32 * 32) * sizeof(short);
 #define LBWD(W)                                                                \
-  hipLaunchKernelGGL((dot_interact_bwd_packed<32, W>), dim3((int)blocks),      \
-                     dim3(block), lds, stream, (const __hip_bfloat16*)gout,    \
+  hipLaunchKernelGGL((dot_interact_bwd_packed_rt<32, W>), dim3(blocks),        \
+                     dim3(W * WAVE), lds, stream, (const __hip_bfloat16*)gout, \
                      (const __hip_bfloat16*)bottom,                            \
                      (const __hip_bfloat16*)packed, perm,                      \
                      (__hip_bfloat16*)gbottom, (__hip_bfloat16*)gpacked, B, F, \
                      D, out_w, tri_n, sb, sp)
-  if (wpb == 2) LBWD(2); else if (wpb == 8) LBWD(8); else LBWD(4);
+  DI_FOR_WPB(LBWD)
 #undef LBWD
 }
+#undef DI_FOR_WPB
 
 void launch_dot_interact_fwd(const void* feats, void* out, int64_t B, int F,
                              int D, int out_w, int tri_n, hipStream_t stream) {
