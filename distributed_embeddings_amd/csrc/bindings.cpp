@@ -78,9 +78,24 @@ void sort_ids_dispatch(torch::Tensor values, int64_t vocab, int64_t nnz,
                        sorted_pos.data_ptr<int32_t>(), stream);
 }
 
+// Optional per-id weights of a weighted lookup: fp32 [nnz] on the GPU, or
+// nullptr when the caller gave none.
+const float* per_id_w_ptr(const std::optional<torch::Tensor>& per_id_w,
+                          const torch::Tensor& values) {
+  if (!per_id_w.has_value()) return nullptr;
+  const torch::Tensor& w = *per_id_w;
+  CHECK_CUDA(w); CHECK_CONTIG(w);
+  TORCH_CHECK(w.dtype() == torch::kFloat32, "per_id_w must be fp32");
+  TORCH_CHECK(w.numel() == values.numel(),
+              "per_id_w must have one weight per id: got ", w.numel(),
+              " for ", values.numel(), " ids");
+  return w.data_ptr<float>();
+}
+
 torch::Tensor csr_lookup_forward(torch::Tensor params, torch::Tensor values,
                                  torch::Tensor row_splits, bool mean,
-                                 bool out_bf16) {
+                                 bool out_bf16,
+                                 std::optional<torch::Tensor> per_id_w) {
   CHECK_CUDA(params); CHECK_CUDA(values); CHECK_CUDA(row_splits);
   CHECK_CONTIG(params); CHECK_CONTIG(values); CHECK_CONTIG(row_splits);
   TORCH_CHECK(params.dtype() == torch::kFloat32 ||
@@ -88,6 +103,7 @@ torch::Tensor csr_lookup_forward(torch::Tensor params, torch::Tensor values,
               "params must be fp32 or bf16");
   TORCH_CHECK(values.dtype() == torch::kInt64, "values must be int64");
   TORCH_CHECK(row_splits.dtype() == torch::kInt64, "row_splits must be int64");
+  const float* w_ptr = per_id_w_ptr(per_id_w, values);
   const int64_t num_rows = row_splits.numel() - 1;
   const int64_t vocab = params.size(0);
   const int width = (int)params.size(1);
@@ -107,7 +123,7 @@ torch::Tensor csr_lookup_forward(torch::Tensor params, torch::Tensor values,
     launch_csr_lookup_forward(params.data_ptr(),
                               params.dtype() == torch::kBFloat16,
                               values.data_ptr<int64_t>(),
-                              row_splits.data_ptr<int64_t>(), nullptr,
+                              row_splits.data_ptr<int64_t>(), w_ptr,
                               out.data_ptr(), out_bf16, num_rows, nnz_in,
                               vocab, width, mean,
                               long_rows.data_ptr<int64_t>(),
@@ -130,12 +146,14 @@ torch::Tensor row_to_split(torch::Tensor rows, int64_t num_rows) {
 // Sorted-segment view of a CSR batch, shared by the sparse backward and the
 // fused update: the ids sorted ascending (OOB masked to the `vocab` sentinel,
 // so last), the source row and mean weight of each sorted position, and one
-// segment per unique valid id.  seg holds num_unique segment starts; each
+// segment per unique valid id.  With user_w (per-id weights of a weighted
+// lookup, or nullptr) sw holds c_r * user_w instead.  seg holds num_unique segment starts; each
 // caller finishes seg[num_unique...] from bounds in its own way.
 struct SortedSegments {
   torch::Tensor sorted_ids;  // [nnz] i64
   torch::Tensor srow;        // [nnz] i64: row of each sorted id
-  torch::Tensor sw;          // [nnz] f32: 1/len of that row (mean only)
+  torch::Tensor sw;          // [nnz] f32: 1/len of that row (mean) times
+                             // the id's weight (weighted); else undefined
   torch::Tensor seg;         // [nnz + 1] i64: first num_unique are set
   torch::Tensor unique_ids;  // [nnz] i64: first num_unique are set
   torch::Tensor num_unique;  // [1] i32, on the device
@@ -145,7 +163,8 @@ struct SortedSegments {
 
 SortedSegments build_sorted_segments(torch::Tensor values,
                                      torch::Tensor row_splits, int64_t vocab,
-                                     bool mean, hipStream_t stream) {
+                                     bool mean, const float* user_w,
+                                     hipStream_t stream) {
   const int64_t nnz = values.numel();
   const int64_t num_rows = row_splits.numel() - 1;
   auto i64 = values.options();
@@ -153,13 +172,15 @@ SortedSegments build_sorted_segments(torch::Tensor values,
   auto f32 = values.options().dtype(torch::kFloat32);
   SortedSegments ss;
 
-  // 1. per-id row ids (+ mean weights keyed by original position).
+  // 1. per-id row ids (+ mean and user weights keyed by original position).
+  const bool has_w = mean || user_w != nullptr;
   auto row_ids = torch::empty({nnz}, i32);
   torch::Tensor w;
-  if (mean) w = torch::empty({nnz}, f32);
-  float* w_ptr = mean ? w.data_ptr<float>() : nullptr;
+  if (has_w) w = torch::empty({nnz}, f32);
+  float* w_ptr = has_w ? w.data_ptr<float>() : nullptr;
   launch_expand_row_ids(row_splits.data_ptr<int64_t>(), num_rows, nnz,
-                        row_ids.data_ptr<int32_t>(), w_ptr, mean, stream);
+                        row_ids.data_ptr<int32_t>(), w_ptr, mean, user_w,
+                        stream);
 
   // 2. mask OOB -> sentinel and radix sort packed (id, position); end_bit
   // covers [0, vocab] inclusive.
@@ -172,7 +193,7 @@ SortedSegments build_sorted_segments(torch::Tensor values,
 
   // 3. permute row ids (+ weights) into sorted order, widened to i64.
   ss.srow = torch::empty({nnz}, i64);
-  if (mean) ss.sw = torch::empty({nnz}, f32);
+  if (has_w) ss.sw = torch::empty({nnz}, f32);
   launch_gather_sorted(sorted_pos.data_ptr<int32_t>(),
                        row_ids.data_ptr<int32_t>(), w_ptr, nnz,
                        ss.srow.data_ptr<int64_t>(), ss.sw_ptr(), stream);
@@ -203,12 +224,15 @@ SortedSegments build_sorted_segments(torch::Tensor values,
 std::vector<torch::Tensor> csr_lookup_backward(torch::Tensor grad_out,
                                                torch::Tensor values,
                                                torch::Tensor row_splits,
-                                               int64_t vocab, bool mean) {
+                                               int64_t vocab, bool mean,
+                                               std::optional<torch::Tensor>
+                                                   per_id_w) {
   CHECK_CUDA(grad_out); CHECK_CUDA(values); CHECK_CUDA(row_splits);
   CHECK_CONTIG(grad_out); CHECK_CONTIG(values); CHECK_CONTIG(row_splits);
   TORCH_CHECK(grad_out.dtype() == torch::kFloat32 ||
                   grad_out.dtype() == torch::kBFloat16,
               "grad_out must be fp32 or bf16");
+  const float* user_w = per_id_w_ptr(per_id_w, values);
   const int64_t nnz = values.numel();
   const int width = (int)grad_out.size(1);
   auto stream = current_stream();
@@ -220,7 +244,8 @@ std::vector<torch::Tensor> csr_lookup_backward(torch::Tensor grad_out,
     return {torch::empty({0}, i64), torch::empty({0, width}, f32)};
   }
 
-  auto ss = build_sorted_segments(values, row_splits, vocab, mean, stream);
+  auto ss = build_sorted_segments(values, row_splits, vocab, mean, user_w,
+                                  stream);
   launch_set_seg_end(ss.seg.data_ptr<int64_t>(),
                      ss.num_unique.data_ptr<int32_t>(),
                      ss.bounds.data_ptr<int64_t>(), stream);
@@ -248,6 +273,51 @@ std::vector<torch::Tensor> csr_lookup_backward(torch::Tensor grad_out,
                               n_work.data_ptr<int32_t>(), stream);
   }
   return {unique_ids, unique_grad};
+}
+
+// Gradient of the per-id weights of a weighted lookup, fp32 [nnz]:
+// dw[k] = c_r * <grad_out[r(k)], params[values[k]]>, 0 for an out-of-range
+// id.  No host sync and torch-allocated buffers only, so it can be captured.
+torch::Tensor csr_lookup_weight_grad(torch::Tensor grad_out,
+                                     torch::Tensor params,
+                                     torch::Tensor values,
+                                     torch::Tensor row_splits, bool mean) {
+  CHECK_CUDA(grad_out); CHECK_CUDA(params); CHECK_CUDA(values);
+  CHECK_CUDA(row_splits);
+  CHECK_CONTIG(grad_out); CHECK_CONTIG(params); CHECK_CONTIG(values);
+  CHECK_CONTIG(row_splits);
+  TORCH_CHECK(grad_out.dtype() == torch::kFloat32 ||
+                  grad_out.dtype() == torch::kBFloat16,
+              "grad_out must be fp32 or bf16");
+  TORCH_CHECK(params.dtype() == torch::kFloat32 ||
+                  params.dtype() == torch::kBFloat16,
+              "params must be fp32 or bf16");
+  TORCH_CHECK(values.dtype() == torch::kInt64, "values must be int64");
+  TORCH_CHECK(row_splits.dtype() == torch::kInt64, "row_splits must be int64");
+  const int64_t nnz = values.numel();
+  const int64_t num_rows = row_splits.numel() - 1;
+  TORCH_CHECK(grad_out.dim() == 2 && params.dim() == 2 &&
+                  grad_out.size(0) == num_rows &&
+                  grad_out.size(1) == params.size(1),
+              "grad_out must be [num_rows, width]");
+  auto stream = current_stream();
+  auto dw = torch::zeros({nnz}, grad_out.options().dtype(torch::kFloat32));
+  if (nnz == 0 || num_rows <= 0) return dw;
+  // zero-filled: a position no row covers reads row 0 and stays in bounds
+  auto row_ids = torch::zeros({nnz}, values.options().dtype(torch::kInt32));
+  launch_expand_row_ids(row_splits.data_ptr<int64_t>(), num_rows, nnz,
+                        row_ids.data_ptr<int32_t>(), nullptr, false, nullptr,
+                        stream);
+  launch_csr_weight_grad(params.data_ptr(),
+                         params.dtype() == torch::kBFloat16,
+                         grad_out.data_ptr(),
+                         grad_out.dtype() == torch::kBFloat16,
+                         values.data_ptr<int64_t>(),
+                         row_ids.data_ptr<int32_t>(),
+                         row_splits.data_ptr<int64_t>(), mean,
+                         dw.data_ptr<float>(), nnz, params.size(0),
+                         (int)params.size(1), stream);
+  return dw;
 }
 
 torch::Tensor integer_lookup(torch::Tensor keys, torch::Tensor table_keys,
@@ -339,7 +409,8 @@ void sparse_row_update(torch::Tensor weight, torch::Tensor state,
 void csr_fused_optimizer_apply(torch::Tensor weight, torch::Tensor state,
                                torch::Tensor values, torch::Tensor row_splits,
                                torch::Tensor grad_out, torch::Tensor lr,
-                               bool mean, bool adagrad, double eps) {
+                               bool mean, bool adagrad, double eps,
+                               std::optional<torch::Tensor> per_id_w) {
   // All-device sorted pipeline (no host sync; hipGraph-capturable):
   // sort (id, pos) -> permute row-ids -> head-flag unique -> segment pad ->
   // one direct update per unique row (long segments chunked with one atomic
@@ -354,6 +425,7 @@ void csr_fused_optimizer_apply(torch::Tensor weight, torch::Tensor state,
   TORCH_CHECK((grad_out.dtype() == torch::kFloat32 ||
                grad_out.dtype() == torch::kBFloat16) &&
               lr.dtype() == torch::kFloat32);
+  const float* user_w = per_id_w_ptr(per_id_w, values);
   const bool wbf16 = weight.dtype() == torch::kBFloat16;
   const int64_t num_rows = row_splits.numel() - 1;
   const int64_t nnz = values.numel();
@@ -365,7 +437,8 @@ void csr_fused_optimizer_apply(torch::Tensor weight, torch::Tensor state,
   auto i32 = values.options().dtype(torch::kInt32);
   auto f32 = grad_out.options().dtype(torch::kFloat32);
 
-  auto ss = build_sorted_segments(values, row_splits, vocab, mean, stream);
+  auto ss = build_sorted_segments(values, row_splits, vocab, mean, user_w,
+                                  stream);
   launch_pad_seg_offsets(ss.seg.data_ptr<int64_t>(), nnz,
                          ss.num_unique.data_ptr<int32_t>(),
                          ss.bounds.data_ptr<int64_t>(), stream);
@@ -532,9 +605,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "CSR segmented gather-reduce forward (gfx950)",
         pybind11::arg("params"), pybind11::arg("values"),
         pybind11::arg("row_splits"), pybind11::arg("mean"),
-        pybind11::arg("out_bf16") = false);
+        pybind11::arg("out_bf16") = false,
+        pybind11::arg("per_id_w") = pybind11::none());
   m.def("csr_lookup_backward", &csr_lookup_backward,
-        "sparse backward: sort + unique + segmented sum (gfx950)");
+        "sparse backward: sort + unique + segmented sum (gfx950)",
+        pybind11::arg("grad_out"), pybind11::arg("values"),
+        pybind11::arg("row_splits"), pybind11::arg("vocab"),
+        pybind11::arg("mean"), pybind11::arg("per_id_w") = pybind11::none());
+  m.def("csr_lookup_weight_grad", &csr_lookup_weight_grad,
+        "gradient of the per-id weights of a weighted lookup (gfx950)",
+        pybind11::arg("grad_out"), pybind11::arg("params"),
+        pybind11::arg("values"), pybind11::arg("row_splits"),
+        pybind11::arg("mean"));
   m.def("row_to_split", &row_to_split, "COO rows -> CSR splits (gfx950)");
   m.def("hash_rehash", &hash_rehash,
         "re-insert occupied (key,value) pairs into a larger hash (gfx950)");
@@ -543,7 +625,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("sparse_row_update", &sparse_row_update,
         "fused sparse SGD/Adagrad/row-wise Adagrad row update (gfx950)");
   m.def("csr_fused_optimizer_apply", &csr_fused_optimizer_apply,
-        "in-backward fused SGD/Adagrad/row-wise Adagrad update (gfx950)");
+        "in-backward fused SGD/Adagrad/row-wise Adagrad update (gfx950)",
+        pybind11::arg("weight"), pybind11::arg("state"),
+        pybind11::arg("values"), pybind11::arg("row_splits"),
+        pybind11::arg("grad_out"), pybind11::arg("lr"), pybind11::arg("mean"),
+        pybind11::arg("adagrad"), pybind11::arg("eps"),
+        pybind11::arg("per_id_w") = pybind11::none());
   m.def("dot_interact_fwd_packed", &dot_interact_fwd_packed,
         "pairwise-dot interaction on (bottom, packed, perm) (MFMA, gfx950)");
   m.def("dot_interact_bwd_packed", &dot_interact_bwd_packed,

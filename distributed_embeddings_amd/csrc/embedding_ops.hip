@@ -17,6 +17,8 @@
 //     radix sort (hand-written, radix_sort.hip; rocPRIM via
 //     DE_USE_ROCPRIM_SORT=1) + head-flag scan unique + segmented sum reusing
 //     the forward kernels with per-id weights (K5-K7 equivalent).
+//   * csr_lookup_weight_grad — gradient of the per-id weights of a weighted
+//     lookup (the forward's per_id_w): one lane group per id, no atomics.
 //   * csr_fused_optimizer_apply — the same pipeline with the SGD, Adagrad or
 //     row-wise Adagrad update applied in place (no host sync;
 //     hipGraph-capturable).
@@ -622,18 +624,22 @@ void launch_row_to_split(const int64_t* rows, int64_t nnz, int64_t num_rows,
 // Backward pipeline.
 // ---------------------------------------------------------------------------
 
-// Expand CSR offsets to per-id row ids (+ mean weights 1/len).
-template <bool MEAN>
+// Expand CSR offsets to per-id row ids and, when MEAN || USER_W, the per-id
+// weight w[k] = c_r * user_w[k]: c_r is 1/len for MEAN and 1 otherwise, and
+// user_w[k] counts as 1 without USER_W.
+template <bool MEAN, bool USER_W>
 __global__ void expand_row_ids(const int64_t* __restrict__ splits,
                                int64_t num_rows, int32_t* __restrict__ row_ids,
-                               float* __restrict__ w) {
+                               float* __restrict__ w,
+                               const float* __restrict__ user_w) {
   const WaveCoord wc = wave_coord();
   for (int64_t row = wc.wave_id; row < num_rows; row += wc.n_waves) {
     const int64_t s = splits[row], e = splits[row + 1];
     const float iw = (MEAN && e > s) ? 1.f / (float)(e - s) : 1.f;
     for (int64_t k = s + wc.lane; k < e; k += WAVE) {
       row_ids[k] = (int32_t)row;
-      if (MEAN) w[k] = iw;
+      if (USER_W) w[k] = iw * user_w[k];
+      else if (MEAN) w[k] = iw;
     }
   }
 }
@@ -694,11 +700,12 @@ size_t csr_backward_temp_bytes(int64_t nnz) {
 // Short segments (the common forward-input shape: hotness 1..tens): one
 // THREAD per row — a wave per hotness-1 row left 63 of 64 lanes idle and
 // made this trivial expansion ~100x slower than its write bandwidth.
-template <bool MEAN>
+template <bool MEAN, bool USER_W>
 __global__ void expand_row_ids_thread(const int64_t* __restrict__ splits,
                                       int64_t num_rows,
                                       int32_t* __restrict__ row_ids,
-                                      float* __restrict__ w) {
+                                      float* __restrict__ w,
+                                      const float* __restrict__ user_w) {
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
        row < num_rows; row += stride) {
@@ -706,27 +713,32 @@ __global__ void expand_row_ids_thread(const int64_t* __restrict__ splits,
     const float iw = (MEAN && e > s) ? 1.f / (float)(e - s) : 1.f;
     for (int64_t k = s; k < e; ++k) {
       row_ids[k] = (int32_t)row;
-      if (MEAN) w[k] = iw;
+      if (USER_W) w[k] = iw * user_w[k];
+      else if (MEAN) w[k] = iw;
     }
   }
 }
 
 void launch_expand_row_ids(const int64_t* splits, int64_t num_rows,
                            int64_t nnz, int32_t* row_ids, float* w, bool mean,
-                           hipStream_t stream) {
+                           const float* user_w, hipStream_t stream) {
   const int block = 256;
   const int64_t ave = num_rows > 0 ? nnz / num_rows : 0;
   dispatch_bool(mean, [&](auto mean_t) {
-    constexpr bool MEAN = decltype(mean_t)::value;
-    float* wp = MEAN ? w : nullptr;
-    if (ave <= 16)
-      hipLaunchKernelGGL(expand_row_ids_thread<MEAN>,
-                         dim3(pick_grid(num_rows, block)), dim3(block), 0,
-                         stream, splits, num_rows, row_ids, wp);
-    else
-      hipLaunchKernelGGL(expand_row_ids<MEAN>,
-                         dim3(pick_grid(num_rows, block / WAVE)), dim3(block),
-                         0, stream, splits, num_rows, row_ids, wp);
+    dispatch_bool(user_w != nullptr, [&](auto user_w_t) {
+      constexpr bool MEAN = decltype(mean_t)::value;
+      constexpr bool USER_W = decltype(user_w_t)::value;
+      float* wp = (MEAN || USER_W) ? w : nullptr;
+      if (ave <= 16)
+        hipLaunchKernelGGL((expand_row_ids_thread<MEAN, USER_W>),
+                           dim3(pick_grid(num_rows, block)), dim3(block), 0,
+                           stream, splits, num_rows, row_ids, wp, user_w);
+      else
+        hipLaunchKernelGGL((expand_row_ids<MEAN, USER_W>),
+                           dim3(pick_grid(num_rows, block / WAVE)),
+                           dim3(block), 0, stream, splits, num_rows, row_ids,
+                           wp, user_w);
+    });
   });
 }
 
@@ -1176,6 +1188,96 @@ void launch_sorted_optimizer_update(void* weight, bool weight_bf16,
           (const GT*)grad_out, lr, nu_ptr, max_segs, width, long_rows,
           long_count, work_items, n_work, long_scratch, adagrad, rowwise,
           stream);
+    });
+  });
+}
+
+// ---------------------------------------------------------------------------
+// Gradient of the per-id weights: dw[k] = c_r * <grad_out[r(k)], table[i_k]>,
+// c_r = 1/len for MEAN and 1 otherwise; exactly 0 for an id outside
+// [0, vocab).
+// ---------------------------------------------------------------------------
+
+// Id-parallel: one lane group per position k, so a long bag needs no long
+// path and nothing is combined with atomics.  Tiling is the forward's: narrow
+// (TILE > 0) gives TILE lanes to a position and 64/TILE positions to a wave;
+// wide gives tile_w lanes x VEC columns and walks the row in n_pass column
+// passes.  Each lane forms its partial dot product in fp32 and tile_sum folds
+// the group in a fixed order, so two calls agree bitwise.  The position loop
+// and the column loop have wave-uniform trip counts; a group past the end or
+// with an out-of-range id stays in step with live == false, because the
+// lanes of one wave shuffle together.  row_ids is launch_expand_row_ids'.
+template <int TILE, int VEC, bool MEAN, typename PT, typename GT>
+__global__ void csr_weight_grad(const PT* __restrict__ params,
+                                const GT* __restrict__ grad_out,
+                                const int64_t* __restrict__ values,
+                                const int32_t* __restrict__ row_ids,
+                                const int64_t* __restrict__ splits,
+                                float* __restrict__ dw, int64_t nnz,
+                                int64_t vocab, int width, int tile_w) {
+  const WaveCoord wc = wave_coord();
+  const TileCoord tc = tile_coord(wc.lane, TILE > 0 ? TILE : tile_w);
+  for (int64_t base = wc.wave_id * tc.rpw; base < nnz;
+       base += wc.n_waves * tc.rpw) {
+    const int64_t k = base + tc.sub;
+    int64_t id = -1, row = 0;
+    if (k < nnz) {
+      id = values[k];
+      row = row_ids[k];
+    }
+    const bool live = id >= 0 && id < vocab;
+    const PT* trow = params + (live ? id : 0) * (int64_t)width;
+    const GT* grow = grad_out + row * (int64_t)width;
+    float dot = 0.f;
+    if constexpr (TILE > 0) {
+      if (live && tc.tl < width)
+        dot = pt_load(&grow[tc.tl]) * pt_load(&trow[tc.tl]);
+      dot = tile_sum(dot, TILE);
+    } else {
+      const int pass_w = tile_w * VEC;
+      const int n_pass = (width + pass_w - 1) / pass_w;
+      for (int p = 0; p < n_pass; ++p) {
+        const int col0 = p * pass_w + tc.tl * VEC;
+        if (live && col0 < width) {
+          float g[VEC], t[VEC];
+          pt_loadv<VEC>(grow + col0, g);
+          pt_loadv<VEC>(trow + col0, t);
+#pragma unroll
+          for (int v = 0; v < VEC; ++v) dot += g[v] * t[v];
+        }
+      }
+      dot = tile_sum(dot, tile_w);
+    }
+    if (k < nnz && tc.tl == 0) {
+      float c = 1.f;
+      if (MEAN && live) c = 1.f / (float)(splits[row + 1] - splits[row]);
+      dw[k] = live ? c * dot : 0.f;
+    }
+  }
+}
+
+void launch_csr_weight_grad(const void* params, bool params_bf16,
+                            const void* grad_out, bool grad_bf16,
+                            const int64_t* values, const int32_t* row_ids,
+                            const int64_t* splits, bool mean, float* dw,
+                            int64_t nnz, int64_t vocab, int width,
+                            hipStream_t stream) {
+  const dim3 block(256);
+  dispatch_width(width, [&](auto tile, auto vec) {
+    constexpr int TILE = decltype(tile)::value, VEC = decltype(vec)::value;
+    const RowTiling t = row_tiling<TILE, VEC>(width, nnz);
+    const dim3 grid(pick_grid(t.row_waves, block.x / WAVE));
+    dispatch_bool(params_bf16, [&](auto p_bf16) {
+      dispatch_bool(grad_bf16, [&](auto g_bf16) {
+        dispatch_bool(mean, [&](auto mean_t) {
+          using PT = storage_t<decltype(p_bf16)>;
+          using GT = storage_t<decltype(g_bf16)>;
+          hipLaunchKernelGGL(
+              (csr_weight_grad<TILE, VEC, decltype(mean_t)::value, PT, GT>),
+              grid, block, 0, stream, (const PT*)params, (const GT*)grad_out,
+              values, row_ids, splits, dw, nnz, vocab, width, t.tile_w);
+        });
+      });
     });
   });
 }

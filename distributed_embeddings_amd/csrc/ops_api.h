@@ -20,9 +20,20 @@ void launch_row_to_split(const int64_t* rows, int64_t nnz, int64_t num_rows,
 
 size_t csr_backward_temp_bytes(int64_t nnz);
 
+// Writes row_ids[k] and, when mean || user_w, w[k] = c_r * user_w[k] with
+// c_r = 1/len for mean and 1 otherwise (user_w == nullptr counts as ones).
 void launch_expand_row_ids(const int64_t* splits, int64_t num_rows,
                            int64_t nnz, int32_t* row_ids, float* w, bool mean,
-                           hipStream_t stream);
+                           const float* user_w, hipStream_t stream);
+
+// dw[k] = c_r * <grad_out[row_ids[k]], params[values[k]]>, 0 for an id
+// outside [0, vocab).  row_ids comes from launch_expand_row_ids.
+void launch_csr_weight_grad(const void* params, bool params_bf16,
+                            const void* grad_out, bool grad_bf16,
+                            const int64_t* values, const int32_t* row_ids,
+                            const int64_t* splits, bool mean, float* dw,
+                            int64_t nnz, int64_t vocab, int width,
+                            hipStream_t stream);
 
 hipError_t run_inclusive_scan_i32(void* temp, size_t temp_bytes,
                                   const int32_t* in, int32_t* out, int64_t n,

@@ -15,7 +15,8 @@ from typing import Callable, Optional, Union
 import torch
 from torch import nn
 
-from ..ops.embedding_lookup import (Ragged, csr_lookup_fused_optimizer,
+from ..ops.embedding_lookup import (Ragged, check_per_id_weights,
+                                    csr_lookup_fused_optimizer,
                                     embedding_lookup)
 
 
@@ -49,6 +50,12 @@ class Embedding(nn.Module):
       * dense ``[d0, ..., dn, hotness]`` + combiner -> ``[d0, ..., dn, output_dim]``
       * ``Ragged`` (2-D CSR) + combiner -> ``[nrows, output_dim]``
       * ``torch.sparse_coo`` 2-D ids + combiner -> ``[nrows, output_dim]``
+
+    Per-sample weights (with a combiner only): ``Ragged.weights``, or
+    ``forward(ids, per_sample_weights)`` with the shape of dense ids.  Each row
+    is scaled by its weight before the reduce; ``mean`` still divides by the
+    number of ids in the bag, not by the weight sum.  Weights that require
+    grad get one, in their own dtype, in every mode of the layer.
     """
 
     def __init__(
@@ -140,20 +147,25 @@ class Embedding(nn.Module):
             self._fused_lr.fill_(float(lr))
 
     def csr_lookup(self, values: torch.Tensor, row_splits: torch.Tensor,
-                   combiner: str, out_dtype=None) -> torch.Tensor:
+                   combiner: str, out_dtype=None,
+                   per_id_w: Optional[torch.Tensor] = None) -> torch.Tensor:
         """CSR lookup through this layer (fused-SGD aware).
 
         ``out_dtype=torch.bfloat16`` makes the HIP kernel store bf16 directly
         (fp32 accumulation; backward consumes bf16 grads natively) — no
-        separate cast kernel on the hot path."""
+        separate cast kernel on the hot path.  ``per_id_w``: one floating
+        weight per id (see ``Ragged.weights``)."""
+        if per_id_w is not None:
+            check_per_id_weights(per_id_w, values.numel())
+            per_id_w = per_id_w.reshape(-1)
         if getattr(self, "_fused_lr", None) is not None and self.training:
             return csr_lookup_fused_optimizer(
                 self.weight, values, row_splits, combiner, self._fused_lr,
                 self._fused_state, self._fused_method != "sgd",
-                self._fused_eps, out_dtype)
+                self._fused_eps, out_dtype, per_id_w)
         from ..ops.embedding_lookup import _CsrLookup
         return _CsrLookup.apply(self.weight, values, row_splits, combiner,
-                                out_dtype)
+                                out_dtype, per_id_w)
 
     def get_config(self) -> dict:
         """Planner-facing config (reference uses keras ``get_config()``)."""
@@ -179,17 +191,26 @@ class Embedding(nn.Module):
             out = self.weight.index_select(0, flat)
         return out.view(*ids.shape, self.output_dim)
 
-    def forward(self, ids: Union[torch.Tensor, Ragged]) -> torch.Tensor:
+    def forward(self, ids: Union[torch.Tensor, Ragged],
+                per_sample_weights: Optional[torch.Tensor] = None) -> torch.Tensor:
         if isinstance(ids, Ragged):
             if self.combiner is None:
                 raise ValueError("Ragged input requires a combiner")
+            if ids.weights is not None and per_sample_weights is not None:
+                raise ValueError("give the weights either as Ragged.weights "
+                                 "or as per_sample_weights, not both")
+            w = ids.weights if ids.weights is not None else per_sample_weights
             return self.csr_lookup(ids.values.long(), ids.row_splits.long(),
-                                    self.combiner)
+                                    self.combiner, per_id_w=w)
+
+        if per_sample_weights is not None and self.combiner is None:
+            raise ValueError("per_sample_weights require a combiner")
 
         if ids.layout == torch.sparse_coo:
             if self.combiner is None:
                 raise ValueError("Sparse input requires a combiner")
-            return embedding_lookup(self.weight, ids, self.combiner)
+            return embedding_lookup(self.weight, ids, self.combiner,
+                                    per_sample_weights)
 
         if ids.dtype != torch.long:
             # parity: reference casts non-int inputs (embedding.py:121-123)
@@ -203,7 +224,19 @@ class Embedding(nn.Module):
                              "(parity: reference embedding.py:133-135)")
         lead_shape = ids.shape[:-1]
         flat2d = ids.reshape(-1, ids.shape[-1])
-        if getattr(self, "_fused_lr", None) is not None and self.training:
+        if per_sample_weights is not None:
+            # weighted: always the CSR path (fused-optimizer aware), with the
+            # weights reshaped alongside N-D ids
+            if per_sample_weights.shape != ids.shape:
+                raise ValueError(
+                    f"per_sample_weights shape {tuple(per_sample_weights.shape)} "
+                    f"does not match ids shape {tuple(ids.shape)}")
+            b, h = flat2d.shape
+            splits = torch.arange(b + 1, device=flat2d.device,
+                                  dtype=torch.long) * h
+            out = self.csr_lookup(flat2d.reshape(-1), splits, self.combiner,
+                                  per_id_w=per_sample_weights.reshape(-1))
+        elif getattr(self, "_fused_lr", None) is not None and self.training:
             # fused in-backward optimizer: dense [b, h] as CSR so the update
             # applies here too (not only for Ragged inputs)
             b, h = flat2d.shape

@@ -32,33 +32,70 @@ class Ragged(NamedTuple):
 
     Equivalent of ``tf.RaggedTensor`` in the reference API (rank-2 only, which
     is all the reference supports — ``embedding.py:129-131``).
+
+    ``weights``: optional 1-D floating tensor aligned with ``values``, one
+    weight per id (``per_sample_weights`` of ``torch.nn.EmbeddingBag``,
+    ``sp_weights`` of ``tf.nn.embedding_lookup_sparse``).  A lookup computes
+    ``c_r * sum_k weights[k] * table[values[k]]`` per row, with ``c_r = 1`` for
+    ``sum`` and ``1 / len(row)`` for ``mean`` (the count mean, not a division
+    by the weight sum).
     """
 
     values: torch.Tensor
     row_splits: torch.Tensor
+    weights: Optional[torch.Tensor] = None
 
     @property
     def nrows(self) -> int:
         return self.row_splits.numel() - 1
 
     @staticmethod
-    def from_row_lengths(values: torch.Tensor, row_lengths: torch.Tensor) -> "Ragged":
+    def from_row_lengths(values: torch.Tensor, row_lengths: torch.Tensor,
+                         weights: Optional[torch.Tensor] = None) -> "Ragged":
         zero = torch.zeros(1, dtype=torch.long, device=row_lengths.device)
         splits = torch.cat([zero, row_lengths.cumsum(0)])
-        return Ragged(values, splits)
+        return Ragged(values, splits, weights)
 
     def row_lengths(self) -> torch.Tensor:
         return self.row_splits[1:] - self.row_splits[:-1]
 
     @staticmethod
-    def from_lists(lists: Sequence[Sequence[int]], device=None) -> "Ragged":
+    def from_lists(lists: Sequence[Sequence[int]],
+                   weights: Optional[Sequence[Sequence[float]]] = None,
+                   device=None) -> "Ragged":
         flat = [i for row in lists for i in row]
         lengths = torch.tensor([len(row) for row in lists], dtype=torch.long, device=device)
         values = torch.tensor(flat, dtype=torch.long, device=device)
-        return Ragged.from_row_lengths(values, lengths)
+        w = None
+        if weights is not None:
+            if [len(row) for row in weights] != [len(row) for row in lists]:
+                raise ValueError("weights must be nested lists of the same "
+                                 "shape as the ids")
+            w = torch.tensor([x for row in weights for x in row],
+                             dtype=torch.float32, device=device)
+        return Ragged.from_row_lengths(values, lengths, w)
+
+    @staticmethod
+    def from_dense(ids: torch.Tensor,
+                   weights: Optional[torch.Tensor] = None) -> "Ragged":
+        """Fixed-hotness ``[b, h]`` ids (and same-shape weights) as CSR."""
+        if ids.dim() != 2:
+            raise ValueError(f"from_dense needs 2-D ids, got {ids.dim()}-D")
+        if weights is not None and weights.shape != ids.shape:
+            raise ValueError(f"weights shape {tuple(weights.shape)} does not "
+                             f"match ids shape {tuple(ids.shape)}")
+        b, h = ids.shape
+        splits = torch.arange(b + 1, device=ids.device, dtype=torch.long) * h
+        return Ragged(ids.reshape(-1), splits,
+                      None if weights is None else weights.reshape(-1))
 
     def to(self, *args, **kwargs) -> "Ragged":
-        return Ragged(self.values.to(*args, **kwargs), self.row_splits.to(*args, **kwargs))
+        values = self.values.to(*args, **kwargs)
+        w = self.weights
+        if w is not None:
+            # ids follow the call; weights only change device, never dtype
+            w = w.to(values.device)
+        return Ragged(values, self.row_splits.to(*args, **kwargs), w)
 
 
 def row_to_split(indices: torch.Tensor, num_rows: int) -> torch.Tensor:
@@ -81,11 +118,13 @@ def _csr_lookup_ref(
     values: torch.Tensor,
     row_splits: torch.Tensor,
     combiner: str,
+    per_id_w: Optional[torch.Tensor] = None,
 ) -> torch.Tensor:
     """Pure-PyTorch CSR segmented gather-reduce (fp32 oracle + CPU path).
 
     Accumulates in fp32 and returns fp32 regardless of the table storage
-    dtype (fp32 or bf16) — matching the HIP kernels.
+    dtype (fp32 or bf16) — matching the HIP kernels.  ``per_id_w`` scales
+    each gathered row before the sum.
     """
     num_rows = row_splits.numel() - 1
     lengths = row_splits[1:] - row_splits[:-1]
@@ -96,6 +135,8 @@ def _csr_lookup_ref(
     safe = torch.where(valid, values, torch.zeros_like(values))
     rows = weight.index_select(0, safe).float()
     rows = rows * valid.unsqueeze(1).to(rows.dtype)
+    if per_id_w is not None:
+        rows = rows * per_id_w.to(rows.dtype).unsqueeze(1)
     seg_ids = torch.repeat_interleave(
         torch.arange(num_rows, device=values.device), lengths
     )
@@ -113,35 +154,45 @@ class _CsrLookup(torch.autograd.Function):
     Forward parity: reference kernels K1-K3 (``embedding_lookup_kernels.cu:
     33-336``).  Backward parity: the sort->unique->segmented-sum pipeline
     (``.cu:603-775``) producing unique ids + summed grad rows.
+
+    ``per_id_w`` (optional, one floating weight per id) scales each row
+    before the reduce; its gradient ``dw[k] = c_r * <grad_out[r(k)],
+    weight[values[k]]>`` is computed only when autograd asks for it.
     """
 
     @staticmethod
-    def forward(ctx, weight, values, row_splits, combiner, out_dtype=None):
-        ctx.save_for_backward(values, row_splits)
+    def forward(ctx, weight, values, row_splits, combiner, out_dtype=None,
+                per_id_w=None):
+        w32 = _kernel_weights(per_id_w)
+        need_dw = per_id_w is not None and ctx.needs_input_grad[5]
+        ctx.save_for_backward(values, row_splits, w32,
+                              weight if need_dw else None)
         ctx.combiner = combiner
         ctx.vocab = weight.shape[0]
         ctx.width = weight.shape[1]
         ctx.wdtype = weight.dtype
+        ctx.dw_dtype = per_id_w.dtype if need_dw else None
         if weight.is_cuda:
             # bf16 out is stored directly by the kernel (no cast kernel);
             # the backward consumes bf16 grads natively too
             return _backend.ops().csr_lookup_forward(
                 weight, values, row_splits, combiner == "mean",
-                out_dtype == torch.bfloat16)
-        out = _csr_lookup_ref(weight, values, row_splits, combiner)
+                out_dtype == torch.bfloat16, w32)
+        out = _csr_lookup_ref(weight, values, row_splits, combiner, w32)
         return out.to(out_dtype) if out_dtype is not None else out
 
     @staticmethod
     def backward(ctx, grad_out):
-        values, row_splits = ctx.saved_tensors
+        values, row_splits, w32, weight = ctx.saved_tensors
         grad_out = grad_out.contiguous()
         if grad_out.is_cuda:
             unique_ids, unique_grad = _backend.ops().csr_lookup_backward(
-                grad_out, values, row_splits, ctx.vocab, ctx.combiner == "mean"
+                grad_out, values, row_splits, ctx.vocab,
+                ctx.combiner == "mean", w32
             )
         else:
             unique_ids, unique_grad = _csr_lookup_backward_ref(
-                grad_out, values, row_splits, ctx.vocab, ctx.combiner
+                grad_out, values, row_splits, ctx.vocab, ctx.combiner, w32
             )
         grad_weight = torch.sparse_coo_tensor(
             unique_ids.unsqueeze(0),
@@ -149,10 +200,45 @@ class _CsrLookup(torch.autograd.Function):
             size=(ctx.vocab, ctx.width),
             is_coalesced=True,
         )
-        return grad_weight, None, None, None, None
+        dw = None
+        if ctx.dw_dtype is not None:
+            dw = _csr_weight_grad(grad_out, weight.detach(), values,
+                                  row_splits, ctx.combiner).to(ctx.dw_dtype)
+        return grad_weight, None, None, None, None, dw
 
 
-def _csr_lookup_backward_ref(grad_out, values, row_splits, vocab, combiner):
+def _kernel_weights(per_id_w):
+    """The contiguous fp32 [nnz] tensor the kernels take (None stays None)."""
+    if per_id_w is None:
+        return None
+    return per_id_w.detach().to(torch.float32).contiguous()
+
+
+def _csr_weight_grad(grad_out, weight, values, row_splits, combiner):
+    """fp32 [nnz] gradient of the per-id weights, HIP kernel or CPU path."""
+    if grad_out.is_cuda:
+        return _backend.ops().csr_lookup_weight_grad(
+            grad_out, weight, values, row_splits, combiner == "mean")
+    return _csr_weight_grad_ref(grad_out, weight, values, row_splits, combiner)
+
+
+def _csr_weight_grad_ref(grad_out, weight, values, row_splits, combiner):
+    """CPU reference: dw[k] = c_r * <grad_out[r(k)], weight[values[k]]> in
+    fp32, exactly 0 for an out-of-range id."""
+    num_rows = row_splits.numel() - 1
+    lengths = (row_splits[1:] - row_splits[:-1]).to(torch.long)
+    seg_ids = torch.repeat_interleave(torch.arange(num_rows, device=values.device), lengths)
+    valid = (values >= 0) & (values < weight.shape[0])
+    safe = torch.where(valid, values, torch.zeros_like(values))
+    rows = weight.index_select(0, safe).float()
+    dot = (grad_out.float().index_select(0, seg_ids) * rows).sum(dim=1)
+    if combiner == "mean":
+        dot = dot / lengths.clamp(min=1).to(dot.dtype).index_select(0, seg_ids)
+    return torch.where(valid, dot, torch.zeros_like(dot))
+
+
+def _csr_lookup_backward_ref(grad_out, values, row_splits, vocab, combiner,
+                             per_id_w=None):
     """CPU reference backward: unique ids + per-unique summed grad rows."""
     num_rows = row_splits.numel() - 1
     lengths = (row_splits[1:] - row_splits[:-1]).to(torch.long)
@@ -161,6 +247,8 @@ def _csr_lookup_backward_ref(grad_out, values, row_splits, vocab, combiner):
     if combiner == "mean":
         w = 1.0 / lengths.clamp(min=1).to(grad_out.dtype)
         g = g * w.index_select(0, seg_ids).unsqueeze(1)
+    if per_id_w is not None:
+        g = g * per_id_w.to(g.dtype).unsqueeze(1)
     valid = (values >= 0) & (values < vocab)
     vals = values[valid]
     g = g[valid]
@@ -183,35 +271,46 @@ class _CsrLookupFusedOptimizer(torch.autograd.Function):
     tensor for SGD).  With ``adagrad`` set, a 1-D fp32 ``[vocab]`` state
     selects row-wise Adagrad: ``state[r] += mean_c(G[r, c]^2)`` on the summed
     row ``G[r]``, then ``w[r] -= lr * G[r] / (sqrt(state[r]) + eps)``.
+
+    With ``per_id_w`` the gradient of the weights is taken from the table as
+    the forward read it: it is computed before the update touches the table.
     """
 
     @staticmethod
     def forward(ctx, weight, values, row_splits, combiner, lr, state, adagrad,
-                eps, out_dtype=None):
-        ctx.save_for_backward(weight, values, row_splits, lr, state)
+                eps, out_dtype=None, per_id_w=None):
+        w32 = _kernel_weights(per_id_w)
+        need_dw = per_id_w is not None and ctx.needs_input_grad[9]
+        ctx.save_for_backward(weight, values, row_splits, lr, state, w32)
         ctx.combiner = combiner
         ctx.adagrad = adagrad
         ctx.eps = eps
+        ctx.dw_dtype = per_id_w.dtype if need_dw else None
         if weight.is_cuda:
             return _backend.ops().csr_lookup_forward(
                 weight, values, row_splits, combiner == "mean",
-                out_dtype == torch.bfloat16)
-        out = _csr_lookup_ref(weight, values, row_splits, combiner)
+                out_dtype == torch.bfloat16, w32)
+        out = _csr_lookup_ref(weight, values, row_splits, combiner, w32)
         return out.to(out_dtype) if out_dtype is not None else out
 
     @staticmethod
     def backward(ctx, grad_out):
-        weight, values, row_splits, lr, state = ctx.saved_tensors
+        weight, values, row_splits, lr, state, w32 = ctx.saved_tensors
         grad_out = grad_out.contiguous()
+        dw = None
         with torch.no_grad():
+            if ctx.dw_dtype is not None:
+                # before the update: the table as the forward read it
+                dw = _csr_weight_grad(grad_out, weight, values, row_splits,
+                                      ctx.combiner).to(ctx.dw_dtype)
             if weight.is_cuda:
                 _backend.ops().csr_fused_optimizer_apply(
                     weight, state, values, row_splits, grad_out, lr,
-                    ctx.combiner == "mean", ctx.adagrad, ctx.eps)
+                    ctx.combiner == "mean", ctx.adagrad, ctx.eps, w32)
             else:
                 unique_ids, unique_grad = _csr_lookup_backward_ref(
                     grad_out.float(), values, row_splits, weight.shape[0],
-                    ctx.combiner)
+                    ctx.combiner, w32)
                 lr_v = lr.item()
                 if ctx.adagrad:
                     sq = unique_grad * unique_grad
@@ -227,23 +326,34 @@ class _CsrLookupFusedOptimizer(torch.autograd.Function):
                 else:
                     weight.index_add_(0, unique_ids,
                                       (unique_grad * (-lr_v)).to(weight.dtype))
-        return (None,) * 9
+        return (None,) * 9 + (dw,)
 
 
 def csr_lookup_fused_sgd(weight, values, row_splits, combiner, lr,
-                         out_dtype=None):
+                         out_dtype=None, per_id_w=None):
     empty = torch.empty(0, dtype=torch.float32, device=weight.device)
     return _CsrLookupFusedOptimizer.apply(weight, values, row_splits, combiner,
-                                          lr, empty, False, 0.0, out_dtype)
+                                          lr, empty, False, 0.0, out_dtype,
+                                          per_id_w)
 
 
 def csr_lookup_fused_optimizer(weight, values, row_splits, combiner, lr, state,
-                               adagrad, eps, out_dtype=None):
+                               adagrad, eps, out_dtype=None, per_id_w=None):
     return _CsrLookupFusedOptimizer.apply(weight, values, row_splits, combiner,
-                                          lr, state, adagrad, eps, out_dtype)
+                                          lr, state, adagrad, eps, out_dtype,
+                                          per_id_w)
 
 
-def _dense_fixed_hotness(weight, ids, combiner):
+def check_per_id_weights(per_id_w, nnz: int) -> None:
+    """Raises ValueError unless per_id_w is a floating tensor of nnz weights."""
+    if not isinstance(per_id_w, torch.Tensor) or not per_id_w.is_floating_point():
+        raise ValueError("per-sample weights must be a floating-point tensor")
+    if per_id_w.numel() != nnz:
+        raise ValueError(f"got {per_id_w.numel()} per-sample weights for "
+                         f"{nnz} ids")
+
+
+def _dense_fixed_hotness(weight, ids, combiner, per_sample_weights=None):
     """Dense [batch, hotness] ids + combiner -> gather + reduce.
 
     Parity: reference dispatcher's native path for fixed hotness
@@ -256,6 +366,8 @@ def _dense_fixed_hotness(weight, ids, combiner):
             0, ids.numel() + 1, ids.shape[1], device=ids.device, dtype=torch.long
         ),
         combiner,
+        None,
+        None if per_sample_weights is None else per_sample_weights.reshape(-1),
     )
     return out
 
@@ -264,6 +376,7 @@ def embedding_lookup(
     weight: torch.Tensor,
     ids: Union[torch.Tensor, Ragged],
     combiner: Optional[str] = None,
+    per_sample_weights: Optional[torch.Tensor] = None,
 ) -> torch.Tensor:
     """Looks up and optionally combines embedding rows.
 
@@ -275,27 +388,66 @@ def embedding_lookup(
       collapses to plain gather.
     * ``torch.sparse_coo`` ids + combiner -> ``row_to_split`` then CSR path.
     * dense ``[batch, hotness]`` + combiner -> gather + reduce.
+
+    Per-sample weights (one floating weight per id; beyond the reference)
+    scale each row before the reduce: ``out[r] = c_r * sum_k w_k * T[i_k]``
+    with ``c_r = 1`` for ``sum`` and ``1 / len(r)`` for ``mean``.  A
+    ``Ragged`` carries them in ``.weights``; dense ``[batch, hotness]`` ids
+    take a same-shape ``per_sample_weights``; sparse COO ids take a sparse
+    COO tensor of the same shape or a 1-D tensor aligned with the coalesced
+    values.  Weights need a combiner, and their gradient flows back in the
+    weights' dtype.
     """
     if combiner not in (None, "sum", "mean"):
         raise ValueError(f"combiner must be None, 'sum' or 'mean', got {combiner!r}")
 
     if isinstance(ids, Ragged):
+        if ids.weights is not None and per_sample_weights is not None:
+            raise ValueError("give the weights either as Ragged.weights or "
+                             "as per_sample_weights, not both")
+        w = ids.weights if ids.weights is not None else per_sample_weights
         if combiner is None:
             raise ValueError("Ragged input requires a combiner ('sum' or 'mean')")
-        return _CsrLookup.apply(weight, ids.values, ids.row_splits, combiner)
+        if w is None:
+            return _CsrLookup.apply(weight, ids.values, ids.row_splits, combiner)
+        check_per_id_weights(w, ids.values.numel())
+        return _CsrLookup.apply(weight, ids.values, ids.row_splits, combiner,
+                                None, w.reshape(-1))
+
+    if per_sample_weights is not None and combiner is None:
+        raise ValueError("per_sample_weights require a combiner "
+                         "('sum' or 'mean')")
 
     if ids.layout == torch.sparse_coo:
         if combiner is None:
             raise ValueError("Sparse input requires a combiner ('sum' or 'mean')")
         ids = ids.coalesce()
         splits = row_to_split(ids.indices().t().contiguous(), ids.shape[0])
-        return _CsrLookup.apply(weight, ids.values(), splits, combiner)
+        if per_sample_weights is None:
+            return _CsrLookup.apply(weight, ids.values(), splits, combiner)
+        w = per_sample_weights
+        if w.layout == torch.sparse_coo:
+            if w.shape != ids.shape:
+                raise ValueError(f"sparse weights shape {tuple(w.shape)} does "
+                                 f"not match ids shape {tuple(ids.shape)}")
+            w = w.coalesce().values()
+        elif w.dim() != 1:
+            raise ValueError("weights for sparse ids must be sparse COO or "
+                             "1-D, aligned with the coalesced values")
+        check_per_id_weights(w, ids.values().numel())
+        return _CsrLookup.apply(weight, ids.values(), splits, combiner, None, w)
 
     if combiner is None:
         return weight.index_select(0, ids.reshape(-1)).view(*ids.shape, weight.shape[1])
 
     if ids.dim() != 2:
         raise ValueError(f"Dense ids with combiner must be 2-D, got {ids.dim()}-D")
+    if per_sample_weights is not None:
+        if per_sample_weights.shape != ids.shape:
+            raise ValueError(
+                f"per_sample_weights shape {tuple(per_sample_weights.shape)} "
+                f"does not match ids shape {tuple(ids.shape)}")
+        check_per_id_weights(per_sample_weights, ids.numel())
     # hotness-1 included: the CSR path keeps the sparse-grad (IndexedSlices)
     # contract and the OOB->zero semantics on every combiner lookup.
-    return _dense_fixed_hotness(weight, ids, combiner)
+    return _dense_fixed_hotness(weight, ids, combiner, per_sample_weights)

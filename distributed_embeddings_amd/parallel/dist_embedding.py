@@ -110,6 +110,11 @@ class DistributedEmbedding(nn.Module):
         model-parallel: each rank passes global-batch ids for the features in
         ``self.local_input_ids()`` only (parity: reference ``dp_input`` arg).
       input_table_map: optional input->table map for shared embeddings.
+
+    Weighted lookups: an input may be a ``Ragged`` with ``weights`` (one
+    floating weight per id); every parallelism mode carries them to the
+    lookup.  Weights are data here: a weights tensor that requires grad is
+    rejected (a single-table :class:`Embedding` does give weight gradients).
     """
 
     def __init__(
@@ -300,6 +305,19 @@ class DistributedEmbedding(nn.Module):
                     "sparse COO inputs are not supported by "
                     "DistributedEmbedding — convert to Ragged "
                     "(single-table Embedding layers do accept sparse)")
+            if isinstance(x, Ragged) and x.weights is not None:
+                if x.weights.requires_grad:
+                    raise ValueError(
+                        "DistributedEmbedding treats Ragged.weights as data "
+                        "and computes no gradient for them; weight gradients "
+                        "are supported by a single-table Embedding layer "
+                        "(pass weights.detach() here)")
+                if (not x.weights.is_floating_point()
+                        or x.weights.numel() != x.values.numel()):
+                    raise ValueError(
+                        f"Ragged.weights must hold one floating weight per "
+                        f"id: got {x.weights.numel()} for "
+                        f"{x.values.numel()} ids")
         if self.dp_input:
             if len(inputs) != len(plan.input_table_map):
                 raise ValueError("wrong number of inputs")
@@ -545,10 +563,17 @@ class DistributedEmbedding(nn.Module):
         """Ragged id redistribution dp->mp (two-phase; parity ``:115-166``).
 
         Dense inputs in the same batch are redistributed by `_dp_to_mp_dense`
-        semantics within one fused pair of all-to-alls.
+        semantics within one fused pair of all-to-alls.  When any input
+        carries weights, one more fp32 all-to-all with the value splits moves
+        them (unweighted inputs send ones); without weights nothing extra is
+        sent.
         """
         plan = self.strategy
         W = self.world_size
+        if W == 1:
+            # nothing to exchange: the inputs are the pairs (and sizing the
+            # receive buffers would cost a host sync per ragged pair)
+            return [col_inputs[i] for i in plan.rank_input_ids[self.rank]]
         # Phase 1: all-to-all of row_lengths for ragged pairs + flat sizes.
         len_parts, len_in_splits = [], []
         for k in range(W):
@@ -580,6 +605,21 @@ class DistributedEmbedding(nn.Module):
                 n += v.numel()
             in_splits.append(n)
         send = torch.cat(send_parts)
+        any_weighted = any(isinstance(x, Ragged) and x.weights is not None
+                           for x in col_inputs)
+        send_w = None
+        if any_weighted:
+            w_parts = []
+            for k in range(W):
+                for i in plan.rank_input_ids[k]:
+                    x = col_inputs[i]
+                    if isinstance(x, Ragged) and x.weights is not None:
+                        w_parts.append(x.weights.reshape(-1).float())
+                    else:
+                        n = x.values.numel() if isinstance(x, Ragged) else x.numel()
+                        w_parts.append(torch.ones(n, dtype=torch.float32,
+                                                  device=send.device))
+            send_w = torch.cat(w_parts)
         # out sizes per src rank: dense sizes are static; ragged from lens.
         lens_by_pair = torch.split(lens, my_rows, dim=1) if lens is not None else []
         per_src_sizes = []  # [W][num_my_pairs]
@@ -596,20 +636,27 @@ class DistributedEmbedding(nn.Module):
             per_src_sizes.append(sizes)
         out_splits = [sum(s) for s in per_src_sizes]
         recv = comm.all_to_all_single(send, out_splits, in_splits)
+        recv_w = None
+        if send_w is not None:
+            recv_w = comm.all_to_all_single(send_w, out_splits, in_splits)
 
         # Reassemble per pair across sources.
-        src_chunks = torch.split(recv, out_splits)
+        def pair_slice(buf, j):
+            chunks = torch.split(buf, out_splits)
+            return torch.cat([chunks[r].split(per_src_sizes[r])[j]
+                              for r in range(W)])
+
         out = []
         ri = 0
         for j, i in enumerate(plan.rank_input_ids[self.rank]):
             x = col_inputs[i]
-            vals = torch.cat([
-                src_chunks[r].split(per_src_sizes[r])[j] for r in range(W)
-            ]) if W > 1 else src_chunks[0].split(per_src_sizes[0])[j]
+            vals = pair_slice(recv, j)
             if isinstance(x, Ragged):
                 pair_lens = lens_by_pair[ri].reshape(-1)  # [W*b]
                 ri += 1
-                out.append(Ragged.from_row_lengths(vals, pair_lens))
+                pair_w = (pair_slice(recv_w, j) if x.weights is not None
+                          else None)
+                out.append(Ragged.from_row_lengths(vals, pair_lens, pair_w))
             else:
                 shape = x.shape
                 out.append(vals.reshape(W * shape[0], *shape[1:]))
@@ -637,6 +684,9 @@ class DistributedEmbedding(nn.Module):
             grp = groups[gi]
             offload = getattr(layer, "_cpu_offload", False)
             if grp.combiner is None:
+                if any(isinstance(pair_ids[j], Ragged) for j in pair_js):
+                    raise ValueError("Ragged input requires a table with a "
+                                     "combiner")
                 # hotness-1 CSR gather: one cat + one cached-offset add for the
                 # whole group (instead of one add per pair per step).
                 metas = [(j, pair_ids[j].shape, pair_ids[j].numel()) for j in pair_js]
@@ -698,6 +748,18 @@ class DistributedEmbedding(nn.Module):
                     return lp
 
                 allvals = _cat_or_view(val_parts)
+                # per-id weights, only when a pair of the group has some:
+                # its unweighted pairs count with ones
+                allw = None
+                if any(isinstance(pair_ids[j], Ragged)
+                       and pair_ids[j].weights is not None for j in pair_js):
+                    allw = torch.cat([
+                        pair_ids[j].weights.reshape(-1).float()
+                        if isinstance(pair_ids[j], Ragged)
+                        and pair_ids[j].weights is not None
+                        else torch.ones(v.numel(), dtype=torch.float32,
+                                        device=device)
+                        for j, v in zip(pair_js, val_parts)])
                 if all_dense:
                     # static shapes: per-element offsets + splits fully cached
                     espec = []
@@ -722,18 +784,23 @@ class DistributedEmbedding(nn.Module):
                     all_lengths = torch.cat(make_len_parts())
                     row_off_vec = self._row_offset_vector(gi, row_offs, device)
                     if row_off_vec is not None:
-                        allvals = allvals + torch.repeat_interleave(row_off_vec,
-                                                                    all_lengths)
+                        # output_size: no host sync to size the result
+                        allvals = allvals + torch.repeat_interleave(
+                            row_off_vec, all_lengths,
+                            output_size=allvals.numel())
                     allsplits = torch.zeros(all_lengths.numel() + 1, dtype=torch.long,
                                             device=device)
                     torch.cumsum(all_lengths, 0, out=allsplits[1:])
                 if offload:
-                    out = embedding_lookup(layer.weight,
-                                           Ragged(allvals.cpu(), allsplits.cpu()),
-                                           grp.combiner).to(allvals.device)
+                    out = embedding_lookup(
+                        layer.weight,
+                        Ragged(allvals.cpu(), allsplits.cpu(),
+                               None if allw is None else allw.cpu()),
+                        grp.combiner).to(allvals.device)
                 else:
                     out = layer.csr_lookup(allvals, allsplits, grp.combiner,
-                                           out_dtype=self._kernel_out_dtype(allvals))
+                                           out_dtype=self._kernel_out_dtype(allvals),
+                                           per_id_w=allw)
                 if getattr(self, "_output_dtype", None) is not None:
                     out = out.to(self._output_dtype)
                 if unsplit:
@@ -1072,9 +1139,13 @@ class DistributedEmbedding(nn.Module):
                 # (OOB contributes zero), reduce-scatter the combined rows.
                 lens_parts = comm.all_gather_uneven(x.row_lengths())
                 vals_parts = comm.all_gather_uneven(x.values)
+                g_w = None
+                if x.weights is not None:
+                    g_w = torch.cat(comm.all_gather_uneven(
+                        x.weights.reshape(-1).float()))
                 g_ragged = Ragged.from_row_lengths(
                     torch.cat(vals_parts) - shard.row_offset,
-                    torch.cat(lens_parts))
+                    torch.cat(lens_parts), g_w)
                 out = layer(g_ragged)                # [W*b, D]
             else:
                 gathered = comm.all_gather(x)        # [W*b, ...]

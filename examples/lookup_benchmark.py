@@ -37,6 +37,8 @@ def main():
     p.add_argument("--width", type=int, default=128)
     p.add_argument("--batch", type=int, default=16384)
     p.add_argument("--max-hotness", type=int, default=500)
+    p.add_argument("--weighted", action="store_true",
+                   help="also time the same shapes with random per-id weights")
     args = p.parse_args()
     device = "cuda" if torch.cuda.is_available() else "cpu"
 
@@ -61,6 +63,22 @@ def main():
         fwd_bwd()
         opt.step()
     print(f"custom fwd+grad+SGD  {timeit(full_step):8.3f} ms")
+
+    if args.weighted:
+        # same ids and table; the weights are data (no gradient for them)
+        w = torch.rand(values.numel(), generator=g).to(device)
+        weighted = Ragged(ragged.values, ragged.row_splits, w)
+        print(f"weighted fwd         {timeit(lambda: emb(weighted)):8.3f} ms")
+
+        def w_fwd_bwd():
+            opt.zero_grad()
+            emb(weighted).sum().backward()
+        print(f"weighted fwd+grad    {timeit(w_fwd_bwd):8.3f} ms")
+
+        def w_full_step():
+            w_fwd_bwd()
+            opt.step()
+        print(f"weighted fwd+g+SGD   {timeit(w_full_step):8.3f} ms")
 
     # torch-native comparison: EmbeddingBag
     bag = torch.nn.EmbeddingBag(args.vocab, args.width, mode="sum",
