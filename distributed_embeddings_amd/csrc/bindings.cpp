@@ -37,29 +37,47 @@ bool use_rocprim_sort() {
   return v == 1;
 }
 
+// Which sort runs: production passes kDefault (the env switch decides); the
+// debug bindings can force either implementation.
+enum class SortChoice { kDefault, kCustom, kRocprim };
+
 // Sorts ids (masking OOB to the `vocab` sentinel) by packing
 // (id << 32 | position) into one u64 array; returns sorted_ids + the sorted
 // original positions.  Hand-written sort by default, rocPRIM via env.
+// variant is custom_radix_sort_keys' (-1: production dispatch).
 void sort_ids_dispatch(torch::Tensor values, int64_t vocab, int64_t nnz,
                        int end_bit, torch::Tensor sorted_ids,
-                       torch::Tensor sorted_pos, hipStream_t stream) {
+                       torch::Tensor sorted_pos, hipStream_t stream,
+                       int variant = -1,
+                       SortChoice sort = SortChoice::kDefault) {
   TORCH_CHECK(end_bit <= 32, "fused table vocab must fit 32 bits");
   TORCH_CHECK(nnz < (int64_t(1) << 32),
               "sort packs positions into 32 bits: nnz must be < 2^32");
+  TORCH_CHECK(variant >= -1 && variant < custom_radix_sort_num_variants(),
+              "sort variant must be -1 or in [0, ",
+              custom_radix_sort_num_variants(), "), got ", variant);
+  const bool rocprim = sort == SortChoice::kRocprim ||
+                       (sort == SortChoice::kDefault && use_rocprim_sort());
   auto u64 = values.options().dtype(torch::kUInt64);
   auto i32 = values.options().dtype(torch::kInt32);
   auto packed = torch::empty({nnz}, u64);
   launch_mask_oob_pack(values.data_ptr<int64_t>(), nnz, vocab,
                        (uint64_t*)packed.data_ptr(), stream);
   auto packed_out = torch::empty({nnz}, u64);
-  if (use_rocprim_sort()) {
+  if (rocprim) {
     size_t temp_bytes = rocprim_sort_keys_temp_bytes(nnz);
     auto temp = torch::empty({(int64_t)temp_bytes},
                              values.options().dtype(torch::kUInt8));
+    // rocPRIM's merge-sort path (mid-sized n) masks a bit range with
+    // T(1) << end_bit, which is undefined at end_bit == 64 and then compares
+    // the positions only.  A range ending at bit 64 (vocab >= 2^31) sorts the
+    // whole key instead: the low words are the distinct ascending positions,
+    // so the order is the stable order on the ids.
+    const int begin_bit = end_bit == 32 ? 0 : 32;
     auto err = run_sort_keys_u64(temp.data_ptr(), temp_bytes,
                                  (const uint64_t*)packed.data_ptr(),
-                                 (uint64_t*)packed_out.data_ptr(), nnz, 32,
-                                 32 + end_bit, stream);
+                                 (uint64_t*)packed_out.data_ptr(), nnz,
+                                 begin_bit, 32 + end_bit, stream);
     TORCH_CHECK(err == hipSuccess, "radix_sort_keys failed");
   } else {
     auto keys_tmp = torch::empty({nnz}, u64);
@@ -71,7 +89,7 @@ void sort_ids_dispatch(torch::Tensor values, int64_t vocab, int64_t nnz,
                            (uint64_t*)keys_tmp.data_ptr(),
                            hist.data_ptr<int32_t>(),
                            scan_sums.data_ptr<int32_t>(), nnz, 32,
-                           32 + end_bit, stream);
+                           32 + end_bit, variant, stream);
   }
   launch_unpack_sorted((const uint64_t*)packed_out.data_ptr(), nnz,
                        sorted_ids.data_ptr<int64_t>(),
@@ -164,7 +182,8 @@ struct SortedSegments {
 SortedSegments build_sorted_segments(torch::Tensor values,
                                      torch::Tensor row_splits, int64_t vocab,
                                      bool mean, const float* user_w,
-                                     hipStream_t stream) {
+                                     hipStream_t stream, int variant = -1,
+                                     SortChoice sort = SortChoice::kDefault) {
   const int64_t nnz = values.numel();
   const int64_t num_rows = row_splits.numel() - 1;
   auto i64 = values.options();
@@ -187,7 +206,7 @@ SortedSegments build_sorted_segments(torch::Tensor values,
   ss.sorted_ids = torch::empty({nnz}, i64);
   auto sorted_pos = torch::empty({nnz}, i32);
   sort_ids_dispatch(values, vocab, nnz, log2_ceil(vocab + 1), ss.sorted_ids,
-                    sorted_pos, stream);
+                    sorted_pos, stream, variant, sort);
   size_t temp_bytes = csr_backward_temp_bytes(nnz);
   auto temp = torch::empty({(int64_t)temp_bytes}, i64.dtype(torch::kUInt8));
 
@@ -273,6 +292,98 @@ std::vector<torch::Tensor> csr_lookup_backward(torch::Tensor grad_out,
                               n_work.data_ptr<int32_t>(), stream);
   }
   return {unique_ids, unique_grad};
+}
+
+// --- test-only windows into the sort pipeline (not public API) -------------
+
+SortChoice parse_sort_choice(const std::string& sort) {
+  if (sort == "default") return SortChoice::kDefault;
+  if (sort == "custom") return SortChoice::kCustom;
+  if (sort == "rocprim") return SortChoice::kRocprim;
+  TORCH_CHECK(false, "sort must be 'default', 'custom' or 'rocprim', got '",
+              sort, "'");
+}
+
+void check_debug_ids(const torch::Tensor& values, int64_t vocab,
+                     int64_t variant) {
+  CHECK_CUDA(values); CHECK_CONTIG(values);
+  TORCH_CHECK(values.dtype() == torch::kInt64, "values must be int64");
+  TORCH_CHECK(vocab >= 1 && vocab < (int64_t(1) << 32),
+              "vocab must be in [1, 2^32), got ", vocab);
+  TORCH_CHECK(variant >= -1 && variant < custom_radix_sort_num_variants(),
+              "sort variant must be -1 or in [0, ",
+              custom_radix_sort_num_variants(), "), got ", variant);
+}
+
+std::vector<int64_t> debug_sort_variant_tiles() {
+  std::vector<int64_t> tiles;
+  for (int v = 0; v < custom_radix_sort_num_variants(); ++v)
+    tiles.push_back(custom_radix_sort_variant_tile(v));
+  return tiles;
+}
+
+// Exactly what sort_ids_dispatch produces: (sorted_ids i64, sorted_pos i32).
+std::tuple<torch::Tensor, torch::Tensor> debug_sort_ids(
+    torch::Tensor values, int64_t vocab, int64_t variant,
+    const std::string& sort) {
+  check_debug_ids(values, vocab, variant);
+  const SortChoice choice = parse_sort_choice(sort);
+  const int64_t nnz = values.numel();
+  auto sorted_ids = torch::empty({nnz}, values.options());
+  auto sorted_pos =
+      torch::empty({nnz}, values.options().dtype(torch::kInt32));
+  if (nnz == 0) return {sorted_ids, sorted_pos};
+  sort_ids_dispatch(values, vocab, nnz, log2_ceil(vocab + 1), sorted_ids,
+                    sorted_pos, current_stream(), (int)variant, choice);
+  return {sorted_ids, sorted_pos};
+}
+
+// build_sorted_segments plus the caller's finish of seg: set_seg_end (the
+// sparse backward) or, with padded, pad_seg_offsets (the fused update).
+// Returns (sorted_ids, srow, sw or None, seg, unique_ids, num_unique, bounds).
+std::tuple<torch::Tensor, torch::Tensor, std::optional<torch::Tensor>,
+           torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor>
+debug_sorted_segments(torch::Tensor values, torch::Tensor row_splits,
+                      int64_t vocab, bool mean,
+                      std::optional<torch::Tensor> per_id_w, bool padded,
+                      int64_t variant, const std::string& sort) {
+  check_debug_ids(values, vocab, variant);
+  CHECK_CUDA(row_splits); CHECK_CONTIG(row_splits);
+  TORCH_CHECK(row_splits.dtype() == torch::kInt64, "row_splits must be int64");
+  const SortChoice choice = parse_sort_choice(sort);
+  const float* user_w = per_id_w_ptr(per_id_w, values);
+  const int64_t nnz = values.numel();
+  // a debug entry point can afford the sync: rows must cover [0, nnz)
+  TORCH_CHECK(row_splits.numel() >= 1, "row_splits must not be empty");
+  TORCH_CHECK(row_splits[0].item<int64_t>() == 0 &&
+                  row_splits[-1].item<int64_t>() == nnz,
+              "row_splits must run from 0 to nnz");
+  auto i64 = values.options();
+  auto i32 = values.options().dtype(torch::kInt32);
+  if (nnz == 0) {
+    std::optional<torch::Tensor> sw;
+    if (mean || user_w)
+      sw = torch::empty({0}, values.options().dtype(torch::kFloat32));
+    return {torch::empty({0}, i64), torch::empty({0}, i64), sw,
+            torch::zeros({1}, i64), torch::empty({0}, i64),
+            torch::zeros({1}, i32), torch::zeros({1}, i64)};
+  }
+  auto stream = current_stream();
+  auto ss = build_sorted_segments(values, row_splits, vocab, mean, user_w,
+                                  stream, (int)variant, choice);
+  if (padded) {
+    launch_pad_seg_offsets(ss.seg.data_ptr<int64_t>(), nnz,
+                           ss.num_unique.data_ptr<int32_t>(),
+                           ss.bounds.data_ptr<int64_t>(), stream);
+  } else {
+    launch_set_seg_end(ss.seg.data_ptr<int64_t>(),
+                       ss.num_unique.data_ptr<int32_t>(),
+                       ss.bounds.data_ptr<int64_t>(), stream);
+  }
+  std::optional<torch::Tensor> sw;
+  if (ss.sw.defined()) sw = ss.sw;
+  return {ss.sorted_ids, ss.srow, sw, ss.seg, ss.unique_ids, ss.num_unique,
+          ss.bounds};
 }
 
 // Gradient of the per-id weights of a weighted lookup, fp32 [nnz]:
@@ -617,6 +728,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("grad_out"), pybind11::arg("params"),
         pybind11::arg("values"), pybind11::arg("row_splits"),
         pybind11::arg("mean"));
+  m.def("debug_sort_ids", &debug_sort_ids,
+        "TESTS ONLY: the backward's id sort -> (sorted_ids, sorted_pos)",
+        pybind11::arg("values"), pybind11::arg("vocab"),
+        pybind11::arg("variant") = -1, pybind11::arg("sort") = "default");
+  m.def("debug_sorted_segments", &debug_sorted_segments,
+        "TESTS ONLY: the backward's sorted-segment view -> (sorted_ids, "
+        "srow, sw or None, seg, unique_ids, num_unique, bounds)",
+        pybind11::arg("values"), pybind11::arg("row_splits"),
+        pybind11::arg("vocab"), pybind11::arg("mean"),
+        pybind11::arg("per_id_w") = pybind11::none(),
+        pybind11::arg("padded") = false, pybind11::arg("variant") = -1,
+        pybind11::arg("sort") = "default");
+  m.def("debug_sort_variant_tiles", &debug_sort_variant_tiles,
+        "TESTS ONLY: keys per block of each radix-sort tile variant");
   m.def("row_to_split", &row_to_split, "COO rows -> CSR splits (gfx950)");
   m.def("hash_rehash", &hash_rehash,
         "re-insert occupied (key,value) pairs into a larger hash (gfx950)");

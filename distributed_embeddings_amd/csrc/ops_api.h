@@ -124,11 +124,16 @@ void launch_relu_bwd_bias_grad(const void* grad_out, const void* y,
                                int64_t num_chunks, hipStream_t stream);
 
 size_t custom_radix_sort_hist_elems(int64_t n);
+int custom_radix_sort_num_variants();
+// keys per block of tile geometry `variant` in [0, num_variants)
+int custom_radix_sort_variant_tile(int variant);
 
+// variant -1: DE_SORT_VARIANT, then dispatch on n (production); a value in
+// [0, num_variants) forces that tile geometry.  The caller rejects the rest.
 void custom_radix_sort_keys(const uint64_t* keys_in, uint64_t* keys_out,
                             uint64_t* keys_tmp, int32_t* hist,
                             int32_t* scan_sums, int64_t n, int begin_bit,
-                            int end_bit, hipStream_t stream);
+                            int end_bit, int variant, hipStream_t stream);
 
 void launch_mask_oob_pack(const int64_t* ids, int64_t n, int64_t vocab,
                           uint64_t* packed, hipStream_t stream);

@@ -212,19 +212,22 @@ const SortVariant kVariants[] = {
     make_variant<8, 16>(),  // 6: tile 8192, 512 threads
     make_variant<16, 8>(),  // 7: tile 8192, 1024 threads
 };
+constexpr int kNumVariants = (int)(sizeof(kVariants) / sizeof(kVariants[0]));
 
 int env_variant() {
   static int v = [] {
     const char* e = std::getenv("DE_SORT_VARIANT");
     if (!e) return -1;
     int i = std::atoi(e);
-    const int nv = (int)(sizeof(kVariants) / sizeof(kVariants[0]));
-    return (i >= 0 && i < nv) ? i : -1;
+    return (i >= 0 && i < kNumVariants) ? i : -1;
   }();
   return v;
 }
 
-const SortVariant& pick_variant(int64_t n) {
+// forced in [0, kNumVariants) wins (tests); -1 is the production choice:
+// the env override, then size dispatch.
+const SortVariant& pick_variant(int64_t n, int forced) {
+  if (forced >= 0 && forced < kNumVariants) return kVariants[forced];
   const int e = env_variant();
   if (e >= 0) return kVariants[e];
   // measured on MI355X (profiles/sort_sweep.md): small-tile 8-wave wins at
@@ -239,8 +242,11 @@ const SortVariant& pick_variant(int64_t n) {
 void custom_radix_sort_keys(const uint64_t* keys_in, uint64_t* keys_out,
                             uint64_t* keys_tmp, int32_t* hist,
                             int32_t* scan_sums, int64_t n, int begin_bit,
-                            int end_bit, hipStream_t stream) {
-  const SortVariant& var = pick_variant(n);
+                            int end_bit, int variant, hipStream_t stream) {
+  // Scratch bounds, for every variant and n: hist holds 256 * cdiv(n, tile)
+  // entries and custom_radix_sort_hist_elems sizes it for the smallest tile;
+  // chunk >= cdiv(m, 2048) gives nb_scan <= 2048 of scan_sums' 4096.
+  const SortVariant& var = pick_variant(n, variant);
   const int tile = var.waves * WAVE * var.ipt;
   const int64_t nblocks = rs_cdiv(n, tile);
   const int passes = (end_bit - begin_bit + 7) / 8;
@@ -269,6 +275,12 @@ void custom_radix_sort_keys(const uint64_t* keys_in, uint64_t* keys_out,
     kin = kout;
     to_tmp = !to_tmp;
   }
+}
+
+int custom_radix_sort_num_variants() { return kNumVariants; }
+
+int custom_radix_sort_variant_tile(int variant) {
+  return kVariants[variant].waves * WAVE * kVariants[variant].ipt;
 }
 
 size_t custom_radix_sort_hist_elems(int64_t n) {
