@@ -9,7 +9,9 @@ embedding hot ops, RCCL collectives over the 8-GPU xGMI full mesh via
 Public API (parity: reference ``distributed_embeddings/__init__.py:17-27``):
 """
 
-from .ops.embedding_lookup import Ragged, embedding_lookup, row_to_split
+from .ops.embedding_lookup import (Ragged, dequantize_rowwise_int8,
+                                   embedding_lookup, quantize_rowwise_int8,
+                                   quantized_embedding_lookup, row_to_split)
 from .layers.embedding import ConcatOneHotEmbedding, Embedding, scaled_uniform_init
 from .layers.integer_lookup import IntegerLookup
 from .parallel.strategy import DistEmbeddingStrategy, TableConfig
@@ -32,6 +34,9 @@ __all__ = [
     "Ragged",
     "embedding_lookup",
     "row_to_split",
+    "quantize_rowwise_int8",
+    "dequantize_rowwise_int8",
+    "quantized_embedding_lookup",
     "Embedding",
     "IntegerLookup",
     "ConcatOneHotEmbedding",

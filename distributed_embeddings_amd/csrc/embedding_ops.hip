@@ -11,6 +11,10 @@
 //     Power-law skew: rows longer than an adaptive threshold are pushed to a
 //     device-side list, expanded to exact (row, 128-id chunk) work items, and
 //     reduced by a second kernel with atomic combine (no host sync).
+//   * csr_lookup_forward_q8 / quantize_rows / dequantize_rows — the same
+//     forward from int8 row-wise quantized tables (width bytes + fp32 scale +
+//     fp32 bias per row, inference only): the wide and long kernels above
+//     instantiated on q8_t, plus the device-side quantizer and its inverse.
 //   * row_to_split        — COO rows -> CSR splits by per-row binary search
 //     (K4 equivalent).
 //   * csr_lookup_backward — rowid expansion + packed (id<<32|pos) keys-only
@@ -172,6 +176,95 @@ __device__ __forceinline__ void wide_accumulate(
 #pragma unroll
     for (int v = 0; v < VEC; ++v) acc[v] += wk * r[v];
   }
+}
+
+// int8 row-wise quantized rows (inference tables): a row of the packed
+// [vocab, width + 8] byte table is width bytes q, then fp32 scale, then fp32
+// bias, and stands for scale * q[c] + bias.  width % 4 == 0, so the row
+// stride is a multiple of 4 and every dword below is aligned.
+struct q8_t { unsigned char b; };
+
+#define Q8_TAIL 8  // bytes of scale + bias behind the quantized columns
+
+__device__ __forceinline__ const unsigned char* q8_row(const q8_t* src,
+                                                       int64_t i, int width) {
+  return reinterpret_cast<const unsigned char*>(src) +
+         i * (int64_t)(width + Q8_TAIL);
+}
+__device__ __forceinline__ unsigned int q8_load4(const unsigned char* row,
+                                                 int col0) {
+  return *reinterpret_cast<const unsigned int*>(row + col0);
+}
+__device__ __forceinline__ float q8_scale(const unsigned char* row, int width) {
+  return *reinterpret_cast<const float*>(row + width);
+}
+__device__ __forceinline__ float q8_bias(const unsigned char* row, int width) {
+  return *reinterpret_cast<const float*>(row + width + 4);
+}
+// byte v of a dword of four quantized columns, as a float (0..255, exact)
+__device__ __forceinline__ float q8_byte(unsigned int q, int v) {
+  return (float)((q >> (8 * v)) & 0xffu);
+}
+
+// The quantized wide gather-accumulate: same contract as wide_accumulate
+// above with `width` the logical width, one dword (VEC == 4 columns) per lane.
+// The bias is factored out of the column sum,
+//   acc[v] = sum_k (w_k * scale_k) * q_k[v]  +  sum_k w_k * bias_k,
+// so a term costs one FMA per column.  An id outside [0, vocab) is skipped in
+// BOTH sums: its loads are pointed at row 0 (the launcher guarantees
+// vocab > 0) and its two coefficients are zeroed, which keeps the loop
+// branch-free.  Four independent id -> row chains are in flight; terms join
+// the sums in k order.
+template <int VEC, bool HAS_W, bool CHECK>
+__device__ __forceinline__ void wide_accumulate(
+    const q8_t* __restrict__ src, const int64_t* __restrict__ idx,
+    const float* __restrict__ w, int64_t vocab, int width, int col0,
+    int64_t ks, int64_t ke, float* acc /* size VEC */) {
+  static_assert(VEC == 4, "a quantized lane owns one dword of columns");
+  constexpr int UNROLL = 4;
+  float aq[VEC] = {0.f, 0.f, 0.f, 0.f};
+  float ab = 0.f;
+  int64_t k = ks;
+  for (; k + UNROLL <= ke; k += UNROLL) {
+    int64_t i[UNROLL];
+    bool ok[UNROLL];
+    unsigned int q[UNROLL];
+    float sc[UNROLL], bi[UNROLL];
+#pragma unroll
+    for (int u = 0; u < UNROLL; ++u) i[u] = idx[k + u];
+#pragma unroll
+    for (int u = 0; u < UNROLL; ++u) {
+      ok[u] = !CHECK || (i[u] >= 0 && i[u] < vocab);
+      const unsigned char* row = q8_row(src, ok[u] ? i[u] : 0, width);
+      q[u] = q8_load4(row, col0);
+      sc[u] = q8_scale(row, width);
+      bi[u] = q8_bias(row, width);
+    }
+#pragma unroll
+    for (int u = 0; u < UNROLL; ++u) {
+      const float wk = HAS_W ? w[k + u] : 1.f;
+      const float ws = ok[u] ? wk * sc[u] : 0.f;
+      ab += ok[u] ? wk * bi[u] : 0.f;
+#pragma unroll
+      for (int v = 0; v < VEC; ++v) aq[v] += ws * q8_byte(q[u], v);
+    }
+  }
+  for (; k < ke; ++k) {
+    const int64_t i = idx[k];
+    const bool ok = !CHECK || (i >= 0 && i < vocab);
+    const unsigned char* row = q8_row(src, ok ? i : 0, width);
+    // all three loads before the selects: a load inside a `?:` arm becomes
+    // a branch of its own, and one-hot lookups live in this loop
+    const unsigned int q = q8_load4(row, col0);
+    const float sc = q8_scale(row, width), bi = q8_bias(row, width);
+    const float wk = HAS_W ? w[k] : 1.f;
+    const float ws = ok ? wk * sc : 0.f;
+    ab += ok ? wk * bi : 0.f;
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) aq[v] += ws * q8_byte(q, v);
+  }
+#pragma unroll
+  for (int v = 0; v < VEC; ++v) acc[v] = aq[v] + ab;
 }
 
 // Narrow strided reduce: lane column tl = lane % TILE sums
@@ -517,6 +610,50 @@ static void dispatch_bool(bool b, F&& f) {
 template <typename IsBf16>
 using storage_t = std::conditional_t<IsBf16::value, bf16_t, float>;
 
+// Adaptive long threshold of the forward: when there are plenty of rows the
+// chip is full without splitting, so only true outliers (>4x the average and
+// >LONG_T) offload; with few rows split aggressively for parallelism.  bf16
+// out: the long-row combine needs fp32 atomics, so the split is disabled —
+// every row reduces in-register in kernel A (callers request bf16 out only on
+// bounded-hotness forwards).
+static int64_t forward_long_threshold(int64_t row_waves, int64_t nnz,
+                                      int64_t num_rows, bool float_out) {
+  if (!float_out) return INT64_MAX;
+  const int64_t ave = num_rows > 0 ? nnz / num_rows : 0;
+  int64_t long_thresh = LONG_T;
+  if (row_waves >= 4096) {
+    long_thresh = 4 * (ave > 0 ? ave : 1);
+    if (long_thresh < LONG_T) long_thresh = LONG_T;
+    if (long_thresh > 8192) long_thresh = 8192;
+  }
+  return long_thresh;
+}
+
+// Kernel A's long-row list starts empty, and so does the work list.
+static void reset_long_lists(int32_t* long_count, int32_t* n_work,
+                             hipStream_t stream) {
+  hipMemsetAsync(long_count, 0, sizeof(int32_t), stream);
+  hipMemsetAsync(n_work, 0, sizeof(int32_t), stream);
+}
+
+// The forward's long pass behind kernel A: expand the long-row list to
+// (row, chunk) work items, then reduce them into the fp32 output.
+template <int TILE, int VEC, bool MEAN, bool HAS_W, typename PT>
+static void launch_forward_long_pass(const PT* params, const int64_t* values,
+                                     const int64_t* splits,
+                                     const float* per_id_w, float* out,
+                                     int64_t vocab, int width,
+                                     int64_t* long_rows, int32_t* long_count,
+                                     int64_t* work_items, int32_t* n_work,
+                                     int tile_w, hipStream_t stream) {
+  const dim3 block(256);
+  hipLaunchKernelGGL(expand_long_work, dim3(512), block, 0, stream, long_rows,
+                     long_count, splits, work_items, n_work);
+  hipLaunchKernelGGL((csr_fwd_long<TILE, VEC, MEAN, HAS_W, PT>), dim3(2048),
+                     block, 0, stream, params, values, splits, per_id_w, out,
+                     vocab, width, long_rows, work_items, n_work, tile_w);
+}
+
 template <typename PT, typename OT>
 static void launch_csr_lookup_forward_t(const PT* params, const int64_t* values,
                                         const int64_t* splits,
@@ -527,27 +664,14 @@ static void launch_csr_lookup_forward_t(const PT* params, const int64_t* values,
                                         int64_t* work_items, int32_t* n_work,
                                         hipStream_t stream) {
   const dim3 block(256);
-  hipMemsetAsync(long_count, 0, sizeof(int32_t), stream);
-  hipMemsetAsync(n_work, 0, sizeof(int32_t), stream);
+  reset_long_lists(long_count, n_work, stream);
   dispatch_width(width, [&](auto tile, auto vec) {
     constexpr int TILE = decltype(tile)::value, VEC = decltype(vec)::value;
     constexpr bool kFloatOut = std::is_same<OT, float>::value;
     const RowTiling t = row_tiling<TILE, VEC>(width, num_rows);
     const dim3 grid(pick_grid(t.row_waves, block.x / WAVE));
-    // Adaptive long threshold: when there are plenty of rows the chip is full
-    // without splitting, so only true outliers (>4x the average and >LONG_T)
-    // offload; with few rows split aggressively for parallelism.
-    const int64_t ave = num_rows > 0 ? nnz / num_rows : 0;
-    int64_t long_thresh = LONG_T;
-    if (t.row_waves >= 4096) {
-      long_thresh = 4 * (ave > 0 ? ave : 1);
-      if (long_thresh < LONG_T) long_thresh = LONG_T;
-      if (long_thresh > 8192) long_thresh = 8192;
-    }
-    // bf16 out: the long-row combine needs fp32 atomics, so disable the
-    // split — every row reduces in-register in kernel A (callers request
-    // bf16 out only on bounded-hotness forwards)
-    if (!kFloatOut) long_thresh = INT64_MAX;
+    const int64_t long_thresh =
+        forward_long_threshold(t.row_waves, nnz, num_rows, kFloatOut);
     dispatch_bool(mean, [&](auto mean_t) {
       dispatch_bool(per_id_w != nullptr, [&](auto has_w_t) {
         constexpr bool MEAN = decltype(mean_t)::value;
@@ -562,14 +686,10 @@ static void launch_csr_lookup_forward_t(const PT* params, const int64_t* values,
                              block, 0, stream, params, values, splits,
                              per_id_w, out, num_rows, vocab, width,
                              long_thresh, long_rows, long_count, t.tile_w);
-        if constexpr (kFloatOut) {
-          hipLaunchKernelGGL(expand_long_work, dim3(512), block, 0, stream,
-                             long_rows, long_count, splits, work_items, n_work);
-          hipLaunchKernelGGL((csr_fwd_long<TILE, VEC, MEAN, HAS_W, PT>),
-                             dim3(2048), block, 0, stream, params, values,
-                             splits, per_id_w, (float*)out, vocab, width,
-                             long_rows, work_items, n_work, t.tile_w);
-        }
+        if constexpr (kFloatOut)
+          launch_forward_long_pass<TILE, VEC, MEAN, HAS_W>(
+              params, values, splits, per_id_w, (float*)out, vocab, width,
+              long_rows, long_count, work_items, n_work, t.tile_w, stream);
       });
     });
   });
@@ -592,6 +712,178 @@ void launch_csr_lookup_forward(const void* params, bool params_bf16,
                                   stream);
     });
   });
+}
+
+// ---------------------------------------------------------------------------
+// int8 row-wise quantized tables: forward, quantize_rows, dequantize_rows.
+// ---------------------------------------------------------------------------
+
+// The quantized forward is csr_fwd_wide / csr_fwd_long instantiated on q8_t
+// at every width: tile_w = pow2(width / 4) lanes own a row (64 rows per wave
+// at width 4, 2 at width 128), the column loop runs from width 260 on, and
+// the long-row list, its expansion and the atomic combine are the fp32
+// tables' own.  vocab must be > 0 (see the q8_t wide_accumulate).
+template <typename OT>
+static void launch_csr_lookup_forward_q8_t(
+    const q8_t* params, const int64_t* values, const int64_t* splits,
+    const float* per_id_w, OT* out, int64_t num_rows, int64_t nnz,
+    int64_t vocab, int width, bool mean, int64_t* long_rows,
+    int32_t* long_count, int64_t* work_items, int32_t* n_work,
+    hipStream_t stream) {
+  constexpr bool kFloatOut = std::is_same<OT, float>::value;
+  const dim3 block(256);
+  reset_long_lists(long_count, n_work, stream);
+  const RowTiling t = row_tiling<0, 4>(width, num_rows);
+  const dim3 grid(pick_grid(t.row_waves, block.x / WAVE));
+  const int64_t long_thresh =
+      forward_long_threshold(t.row_waves, nnz, num_rows, kFloatOut);
+  dispatch_bool(mean, [&](auto mean_t) {
+    dispatch_bool(per_id_w != nullptr, [&](auto has_w_t) {
+      constexpr bool MEAN = decltype(mean_t)::value;
+      constexpr bool HAS_W = decltype(has_w_t)::value;
+      hipLaunchKernelGGL((csr_fwd_wide<4, MEAN, HAS_W, q8_t, OT>), grid, block,
+                         0, stream, params, values, splits, per_id_w, out,
+                         num_rows, vocab, width, long_thresh, long_rows,
+                         long_count, t.tile_w);
+      if constexpr (kFloatOut)
+        launch_forward_long_pass<0, 4, MEAN, HAS_W>(
+            params, values, splits, per_id_w, (float*)out, vocab, width,
+            long_rows, long_count, work_items, n_work, t.tile_w, stream);
+    });
+  });
+}
+
+void launch_csr_lookup_forward_q8(const void* packed, const int64_t* values,
+                                  const int64_t* splits, const float* per_id_w,
+                                  void* out, bool out_bf16, int64_t num_rows,
+                                  int64_t nnz, int64_t vocab, int width,
+                                  bool mean, int64_t* long_rows,
+                                  int32_t* long_count, int64_t* work_items,
+                                  int32_t* n_work, hipStream_t stream) {
+  dispatch_bool(out_bf16, [&](auto o_bf16) {
+    using OT = storage_t<decltype(o_bf16)>;
+    launch_csr_lookup_forward_q8_t((const q8_t*)packed, values, splits,
+                                   per_id_w, (OT*)out, num_rows, nnz, vocab,
+                                   width, mean, long_rows, long_count,
+                                   work_items, n_work, stream);
+  });
+}
+
+// min / max of v over the `tile` (pow2 <= WAVE) lanes of the caller's lane
+// group, by xor butterfly as in tile_sum: every lane of the group calls it.
+__device__ __forceinline__ float tile_min(float v, int tile) {
+  for (int off = tile >> 1; off > 0; off >>= 1) v = fminf(v, __shfl_xor(v, off));
+  return v;
+}
+__device__ __forceinline__ float tile_max(float v, int tile) {
+  for (int off = tile >> 1; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off));
+  return v;
+}
+
+// quantize_rows: in [n, width] fp32 or bf16 -> packed [n, width + 8].  One
+// tile_w-lane group per row, four columns per lane and trip.  Pass 1 finds
+// the row's min and max (butterfly inside the group), pass 2 re-reads the
+// lane's columns — they are in L1/L2 — quantizes them and stores one dword;
+// the group's first lane stores scale and bias.
+//   bias = min, scale = (max - min) / 255,
+//   q = clamp(rint((x - bias) * (255 / (max - min))), 0, 255)
+// and q = 0, scale = 0 for a constant row, which then dequantizes to bias.
+// A group whose row is past n keeps running with live == false, so the
+// shuffles never read a lane that has left the loop.
+template <typename ST>
+__global__ void quantize_rows_kernel(const ST* __restrict__ in,
+                                     unsigned char* __restrict__ out,
+                                     int64_t n, int width, int tile_w) {
+  const WaveCoord wc = wave_coord();
+  const TileCoord tc = tile_coord(wc.lane, tile_w);
+  for (int64_t base = wc.wave_id * tc.rpw; base < n;
+       base += wc.n_waves * tc.rpw) {
+    const int64_t row = base + tc.sub;
+    const bool live = row < n;
+    const ST* src = in + (live ? row : 0) * (int64_t)width;
+    float lo = INFINITY, hi = -INFINITY;
+    if (live) {
+      for (int col0 = tc.tl * 4; col0 < width; col0 += tile_w * 4) {
+        float x[4];
+        pt_load4(src + col0, x);
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+          lo = fminf(lo, x[v]);
+          hi = fmaxf(hi, x[v]);
+        }
+      }
+    }
+    lo = tile_min(lo, tile_w);
+    hi = tile_max(hi, tile_w);
+    if (!live) continue;
+    const float range = hi - lo;
+    const float scale = range / 255.f;
+    const float inv = range > 0.f ? 255.f / range : 0.f;
+    unsigned char* dst = out + row * (int64_t)(width + Q8_TAIL);
+    for (int col0 = tc.tl * 4; col0 < width; col0 += tile_w * 4) {
+      float x[4];
+      pt_load4(src + col0, x);
+      unsigned int q = 0;
+#pragma unroll
+      for (int v = 0; v < 4; ++v) {
+        const float r = fminf(fmaxf(rintf((x[v] - lo) * inv), 0.f), 255.f);
+        q |= (unsigned int)r << (8 * v);
+      }
+      *reinterpret_cast<unsigned int*>(dst + col0) = q;
+    }
+    if (tc.tl == 0) {
+      *reinterpret_cast<float*>(dst + width) = scale;
+      *reinterpret_cast<float*>(dst + width + 4) = lo;
+    }
+  }
+}
+
+// dequantize_rows: packed [n, width + 8] -> fp32 [n, width] as
+// fma(scale, q, bias): one rounding per element, written as an explicit fmaf
+// so the bits do not depend on the compiler's contraction choices.
+__global__ void dequantize_rows_kernel(const q8_t* __restrict__ in,
+                                       float* __restrict__ out, int64_t n,
+                                       int width, int tile_w) {
+  const WaveCoord wc = wave_coord();
+  const TileCoord tc = tile_coord(wc.lane, tile_w);
+  for (int64_t base = wc.wave_id * tc.rpw; base < n;
+       base += wc.n_waves * tc.rpw) {
+    const int64_t row = base + tc.sub;
+    if (row >= n) continue;
+    const unsigned char* src = q8_row(in, row, width);
+    const float scale = q8_scale(src, width), bias = q8_bias(src, width);
+    for (int col0 = tc.tl * 4; col0 < width; col0 += tile_w * 4) {
+      const unsigned int q = q8_load4(src, col0);
+      float x[4];
+#pragma unroll
+      for (int v = 0; v < 4; ++v) x[v] = fmaf(scale, q8_byte(q, v), bias);
+      pt_store4(out + row * (int64_t)width + col0, x);
+    }
+  }
+}
+
+void launch_quantize_rows_q8(const void* in, bool in_bf16, void* packed,
+                             int64_t n, int width, hipStream_t stream) {
+  if (n <= 0) return;
+  const dim3 block(256);
+  const RowTiling t = row_tiling<0, 4>(width, n);
+  const dim3 grid(pick_grid(t.row_waves, block.x / WAVE));
+  dispatch_bool(in_bf16, [&](auto i_bf16) {
+    using ST = storage_t<decltype(i_bf16)>;
+    hipLaunchKernelGGL((quantize_rows_kernel<ST>), grid, block, 0, stream,
+                       (const ST*)in, (unsigned char*)packed, n, width,
+                       t.tile_w);
+  });
+}
+
+void launch_dequantize_rows_q8(const void* packed, float* out, int64_t n,
+                               int width, hipStream_t stream) {
+  if (n <= 0) return;
+  const dim3 block(256);
+  const RowTiling t = row_tiling<0, 4>(width, n);
+  const dim3 grid(pick_grid(t.row_waves, block.x / WAVE));
+  hipLaunchKernelGGL(dequantize_rows_kernel, grid, block, 0, stream,
+                     (const q8_t*)packed, out, n, width, t.tile_w);
 }
 
 // ---------------------------------------------------------------------------

@@ -15,6 +15,23 @@ void launch_csr_lookup_forward(const void* params, bool params_bf16,
                                int32_t* long_count, int64_t* work_items,
                                int32_t* n_work, hipStream_t stream);
 
+// int8 row-wise quantized tables.  packed is [vocab, width + 8] bytes: per
+// row width bytes q, fp32 scale, fp32 bias; the row stands for
+// scale * q + bias.  width % 4 == 0, and the forward needs vocab > 0.
+void launch_csr_lookup_forward_q8(const void* packed, const int64_t* values,
+                                  const int64_t* splits, const float* per_id_w,
+                                  void* out, bool out_bf16, int64_t num_rows,
+                                  int64_t nnz, int64_t vocab, int width,
+                                  bool mean, int64_t* long_rows,
+                                  int32_t* long_count, int64_t* work_items,
+                                  int32_t* n_work, hipStream_t stream);
+// in: [n, width] fp32 or bf16, aligned to four elements; packed:
+// [n, width + 8].
+void launch_quantize_rows_q8(const void* in, bool in_bf16, void* packed,
+                             int64_t n, int width, hipStream_t stream);
+void launch_dequantize_rows_q8(const void* packed, float* out, int64_t n,
+                               int width, hipStream_t stream);
+
 void launch_row_to_split(const int64_t* rows, int64_t nnz, int64_t num_rows,
                          int64_t* splits, hipStream_t stream);
 

@@ -15,9 +15,12 @@ from typing import Callable, Optional, Union
 import torch
 from torch import nn
 
-from ..ops.embedding_lookup import (Ragged, check_per_id_weights,
+from ..ops.embedding_lookup import (Ragged, _csr_lookup_q8,
+                                    check_per_id_weights,
                                     csr_lookup_fused_optimizer,
-                                    embedding_lookup)
+                                    dequantize_rowwise_int8, embedding_lookup,
+                                    quantize_rowwise_int8,
+                                    quantized_embedding_lookup)
 
 
 def _default_init(weight: torch.Tensor) -> None:
@@ -56,6 +59,13 @@ class Embedding(nn.Module):
     is scaled by its weight before the reduce; ``mean`` still divides by the
     number of ids in the bag, not by the weight sum.  Weights that require
     grad get one, in their own dtype, in every mode of the layer.
+
+    Serving from int8: :meth:`quantize_` replaces the ``weight`` parameter by
+    the buffer ``qweight`` (int8 row-wise packed, ``[input_dim,
+    output_dim + 8]`` uint8, see ``quantize_rowwise_int8``);
+    :meth:`from_quantized` builds such a layer from packed bytes.  A quantized
+    layer serves every input kind, forward only: its outputs never require
+    grad and it takes no optimizer.
     """
 
     def __init__(
@@ -87,9 +97,84 @@ class Embedding(nn.Module):
         # reference's reliance on TF GPU OOB-gather-zeros
         # (dist_model_parallel.py:889-904).
         self._oob_zero = False
+        self.quantized = False
 
     def extra_repr(self) -> str:
-        return f"input_dim={self.input_dim}, output_dim={self.output_dim}, combiner={self.combiner}"
+        s = f"input_dim={self.input_dim}, output_dim={self.output_dim}, combiner={self.combiner}"
+        return s + ", quantized=int8" if self.quantized else s
+
+    # ------------------------------------------------- int8 row-wise serving
+
+    def quantize_(self, chunk_rows: int = 1 << 20):
+        """Converts the table in place to int8 row-wise storage: registers
+        the buffer ``qweight``, removes the ``weight`` parameter (its memory
+        is released) and returns ``self``.  The table stays on its device —
+        a CPU-offloaded table stays on the CPU.  One-way: load the weights
+        first, then quantize, then serve."""
+        if self.quantized:
+            return self
+        if getattr(self, "_fused_lr", None) is not None:
+            raise RuntimeError("a layer with a fused optimizer enabled "
+                               "cannot be quantized: it is being trained")
+        packed = quantize_rowwise_int8(self.weight.detach(), chunk_rows)
+        # a model-parallel shard stays shard-local
+        packed.de_local = getattr(self.weight, "de_local", False)
+        del self._parameters["weight"]
+        self.register_buffer("qweight", packed)
+        self.quantized = True
+        return self
+
+    @classmethod
+    def from_quantized(cls, packed: torch.Tensor,
+                       combiner: Optional[str] = None) -> "Embedding":
+        """A quantized layer around int8 row-wise ``packed`` bytes
+        (``[input_dim, output_dim + 8]`` uint8); no fp32 table is ever
+        allocated."""
+        if combiner not in (None, "sum", "mean"):
+            raise ValueError(f"invalid combiner {combiner!r}")
+        if (not isinstance(packed, torch.Tensor) or packed.dtype != torch.uint8
+                or packed.dim() != 2 or packed.shape[0] <= 0
+                or packed.shape[1] < 12 or (packed.shape[1] - 8) % 4 != 0):
+            raise ValueError("packed must be uint8 [input_dim, output_dim + 8] "
+                             "with output_dim a positive multiple of 4")
+        self = cls.__new__(cls)
+        nn.Module.__init__(self)
+        self.input_dim = int(packed.shape[0])
+        self.output_dim = int(packed.shape[1]) - 8
+        self.combiner = combiner
+        self.sparse_grad = True
+        self._oob_zero = False
+        self.register_buffer("qweight", packed.detach().contiguous())
+        self.quantized = True
+        return self
+
+    def dequantized_weight(self) -> torch.Tensor:
+        """fp32 ``[input_dim, output_dim]`` values the quantized table
+        stands for."""
+        if not self.quantized:
+            raise RuntimeError("dequantized_weight() needs a quantized layer")
+        return dequantize_rowwise_int8(self.qweight)
+
+    def _quantized_forward(self, ids, per_sample_weights):
+        if isinstance(ids, Ragged) or ids.layout == torch.sparse_coo:
+            return quantized_embedding_lookup(self.qweight, ids, self.combiner,
+                                              per_sample_weights)
+        if self.combiner is None:
+            return quantized_embedding_lookup(self.qweight, ids)
+        if ids.dim() < 2:
+            raise ValueError("ids with a combiner must have a hotness dimension "
+                             "(parity: reference embedding.py:133-135)")
+        if (per_sample_weights is not None
+                and per_sample_weights.shape != ids.shape):
+            raise ValueError(
+                f"per_sample_weights shape {tuple(per_sample_weights.shape)} "
+                f"does not match ids shape {tuple(ids.shape)}")
+        h = ids.shape[-1]
+        out = quantized_embedding_lookup(
+            self.qweight, ids.reshape(-1, h), self.combiner,
+            None if per_sample_weights is None
+            else per_sample_weights.reshape(-1, h))
+        return out.view(*ids.shape[:-1], self.output_dim)
 
     def _apply(self, fn, recurse=True):
         # CPU-offloaded tables are pinned: .to('cuda') / .cuda() on the parent
@@ -115,6 +200,9 @@ class Embedding(nn.Module):
         the row's summed gradient).  Calling it again replaces the state."""
         if method not in ("sgd", "adagrad", "rowwise_adagrad"):
             raise ValueError(f"unknown fused optimizer {method!r}")
+        if self.quantized:
+            raise RuntimeError("a quantized (int8) table is inference-only: "
+                               "it takes no optimizer")
         for name in ("_fused_lr", "_fused_state"):  # allow re-configuring
             if name in self._buffers:
                 del self._buffers[name]
@@ -141,6 +229,9 @@ class Embedding(nn.Module):
         return self
 
     def set_fused_lr(self, lr: float):
+        if self.quantized:
+            raise RuntimeError("a quantized (int8) table is inference-only: "
+                               "it takes no optimizer")
         if getattr(self, "_fused_lr", None) is None:
             raise RuntimeError("enable_fused_sgd() first")
         with torch.no_grad():
@@ -158,6 +249,10 @@ class Embedding(nn.Module):
         if per_id_w is not None:
             check_per_id_weights(per_id_w, values.numel())
             per_id_w = per_id_w.reshape(-1)
+        if self.quantized:
+            with torch.no_grad():
+                return _csr_lookup_q8(self.qweight, values, row_splits,
+                                      combiner, out_dtype, per_id_w)
         if getattr(self, "_fused_lr", None) is not None and self.training:
             return csr_lookup_fused_optimizer(
                 self.weight, values, row_splits, combiner, self._fused_lr,
@@ -193,6 +288,8 @@ class Embedding(nn.Module):
 
     def forward(self, ids: Union[torch.Tensor, Ragged],
                 per_sample_weights: Optional[torch.Tensor] = None) -> torch.Tensor:
+        if self.quantized:
+            return self._quantized_forward(ids, per_sample_weights)
         if isinstance(ids, Ragged):
             if self.combiner is None:
                 raise ValueError("Ragged input requires a combiner")

@@ -1,1 +1,3 @@
-from .embedding_lookup import Ragged, embedding_lookup, row_to_split
+from .embedding_lookup import (Ragged, dequantize_rowwise_int8,
+                               embedding_lookup, quantize_rowwise_int8,
+                               quantized_embedding_lookup, row_to_split)

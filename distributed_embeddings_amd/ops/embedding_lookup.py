@@ -451,3 +451,204 @@ def embedding_lookup(
     # hotness-1 included: the CSR path keeps the sparse-grad (IndexedSlices)
     # contract and the OOB->zero semantics on every combiner lookup.
     return _dense_fixed_hotness(weight, ids, combiner, per_sample_weights)
+
+
+# ---------------------------------------------------------------------------
+# int8 row-wise quantized tables (inference only)
+# ---------------------------------------------------------------------------
+#
+# Storage: uint8 [vocab, width + 8], contiguous.  Row i holds width bytes
+# q[i, c] in 0..255, then fp32 scale[i], then fp32 bias[i] (native byte
+# order), and stands for scale[i] * q[i, c] + bias[i] — byte for byte the
+# "fused 8-bit rowwise" layout of FBGEMM / torch.ops.quantized.
+# embedding_bag_byte_prepack.  width % 4 == 0 keeps every dword, scale and
+# bias 4-byte aligned.
+
+_Q8_TAIL = 8
+
+
+def _check_packed(packed: torch.Tensor) -> int:
+    """Validates an int8 row-wise packed table and returns its width."""
+    if not isinstance(packed, torch.Tensor) or packed.dtype != torch.uint8:
+        raise ValueError("a quantized table must be a uint8 tensor")
+    if (packed.dim() != 2 or packed.shape[1] < _Q8_TAIL + 4
+            or (packed.shape[1] - _Q8_TAIL) % 4 != 0):
+        raise ValueError(
+            f"a quantized table must be [vocab, width + 8] with width a "
+            f"positive multiple of 4, got {tuple(packed.shape)}")
+    return packed.shape[1] - _Q8_TAIL
+
+
+def _quantize_rows_ref(x: torch.Tensor) -> torch.Tensor:
+    """Pure-torch quantizer of fp32 [n, width] rows (CPU path)."""
+    n, width = x.shape
+    out = torch.empty(n, width + _Q8_TAIL, dtype=torch.uint8, device=x.device)
+    if n == 0:
+        return out
+    lo = x.min(dim=1, keepdim=True).values
+    hi = x.max(dim=1, keepdim=True).values
+    rng = hi - lo
+    scale = rng / 255
+    inv = torch.where(rng > 0, 255 / rng, torch.zeros_like(rng))
+    q = torch.round((x - lo) * inv).clamp_(0, 255)
+    out[:, :width] = q.to(torch.uint8)
+    tail = torch.cat([scale, lo], dim=1).contiguous()
+    out[:, width:] = tail.view(torch.uint8)
+    return out
+
+
+def quantize_rowwise_int8(weight: torch.Tensor,
+                          chunk_rows: Optional[int] = None) -> torch.Tensor:
+    """fp32 or bf16 ``[vocab, width]`` -> int8 row-wise packed
+    ``[vocab, width + 8]`` uint8 on the same device.
+
+    Per row: ``bias = min``, ``scale = (max - min) / 255`` and
+    ``q = clamp(rint((x - bias) * (255 / (max - min))), 0, 255)``; a
+    constant row stores ``q = 0`` and dequantizes exactly.  ``width`` must be
+    a multiple of 4.  On the device the HIP kernel converts ``chunk_rows``
+    rows per launch (all of them by default); the temporaries are bounded by
+    the chunk.
+    """
+    if weight.dim() != 2:
+        raise ValueError(f"weight must be 2-D, got {weight.dim()}-D")
+    if weight.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError("weight must be fp32 or bf16")
+    n, width = weight.shape
+    if width < 4 or width % 4 != 0:
+        raise ValueError(f"int8 row-wise quantization needs a width that is "
+                         f"a multiple of 4, got width {width}")
+    if chunk_rows is not None and chunk_rows <= 0:
+        raise ValueError("chunk_rows must be positive")
+    weight = weight.detach()
+    step = n if chunk_rows is None else int(chunk_rows)
+
+    def convert(rows):
+        rows = rows.contiguous()
+        if rows.is_cuda:
+            return _backend.ops().quantize_rows_q8(rows)
+        return _quantize_rows_ref(rows.float())
+
+    if step >= n:
+        return convert(weight)
+    out = torch.empty(n, width + _Q8_TAIL, dtype=torch.uint8,
+                      device=weight.device)
+    for s in range(0, n, step):
+        out[s:s + step].copy_(convert(weight[s:s + step]))
+    return out
+
+
+def dequantize_rowwise_int8(packed: torch.Tensor) -> torch.Tensor:
+    """int8 row-wise packed ``[vocab, width + 8]`` -> fp32 ``[vocab, width]``:
+    ``fma(scale, q, bias)``, one fp32 rounding per element.
+
+    The CPU path evaluates in fp64 and rounds once: ``scale * q`` is exact
+    there (24 x 8 bits), and so is the sum unless the two terms are more than
+    2**21 apart in magnitude, so the result is the fused multiply-add's."""
+    width = _check_packed(packed)
+    packed = packed.contiguous()
+    if packed.is_cuda:
+        return _backend.ops().dequantize_rows_q8(packed)
+    tail = packed[:, width:].contiguous().view(torch.float32).double()
+    return (packed[:, :width].double() * tail[:, 0:1] + tail[:, 1:2]).float()
+
+
+def _csr_lookup_q8(packed, values, row_splits, combiner, out_dtype=None,
+                   per_id_w=None):
+    """CSR lookup from a packed table: HIP kernel, or on the CPU
+    ``_csr_lookup_ref`` over the gathered, dequantized rows."""
+    w32 = _kernel_weights(per_id_w)
+    if packed.is_cuda:
+        return _backend.ops().csr_lookup_forward_q8(
+            packed, values, row_splits, combiner == "mean",
+            out_dtype == torch.bfloat16, w32)
+    vocab = packed.shape[0]
+    valid = (values >= 0) & (values < vocab)
+    # dequantize only the rows the batch touches, and append one zero row:
+    # an out-of-range id becomes that row's id, so the gathered table is
+    # never empty, even when no id of the call is valid
+    pos = torch.cumsum(valid.to(torch.long), 0) - 1
+    rows = dequantize_rowwise_int8(packed.index_select(0, values[valid]))
+    n_valid = rows.shape[0]
+    rows = torch.cat([rows, rows.new_zeros(1, rows.shape[1])])
+    local = torch.where(valid, pos, torch.full_like(pos, n_valid))
+    out = _csr_lookup_ref(rows, local, row_splits, combiner, w32)
+    return out.to(out_dtype) if out_dtype is not None else out
+
+
+def quantized_embedding_lookup(
+    packed: torch.Tensor,
+    ids: Union[torch.Tensor, Ragged],
+    combiner: Optional[str] = None,
+    per_sample_weights: Optional[torch.Tensor] = None,
+    out_dtype: Optional[torch.dtype] = None,
+) -> torch.Tensor:
+    """:func:`embedding_lookup` from an int8 row-wise quantized table
+    (:func:`quantize_rowwise_int8`), forward only.
+
+    Same routing: dense ids of any rank without a combiner (a hotness-1
+    ``sum``), dense ``[batch, hotness]``, ``Ragged`` (with or without
+    ``.weights``) and sparse COO ids with one.  Rows are dequantized on the
+    fly and accumulated in fp32; an id outside ``[0, vocab)`` contributes a
+    zero row.  The result is fp32, or ``out_dtype=torch.bfloat16``, and never
+    requires grad.
+    """
+    if combiner not in (None, "sum", "mean"):
+        raise ValueError(f"combiner must be None, 'sum' or 'mean', got {combiner!r}")
+    if out_dtype not in (None, torch.float32, torch.bfloat16):
+        raise ValueError("out_dtype must be None, float32 or bfloat16")
+    width = _check_packed(packed)
+
+    def run(values, splits, comb, w=None):
+        if w is not None:
+            check_per_id_weights(w, values.numel())
+            w = w.reshape(-1)
+        with torch.no_grad():
+            return _csr_lookup_q8(packed, values.long().contiguous(),
+                                  splits.long().contiguous(), comb, out_dtype,
+                                  w)
+
+    if isinstance(ids, Ragged):
+        if ids.weights is not None and per_sample_weights is not None:
+            raise ValueError("give the weights either as Ragged.weights or "
+                             "as per_sample_weights, not both")
+        if combiner is None:
+            raise ValueError("Ragged input requires a combiner ('sum' or 'mean')")
+        w = ids.weights if ids.weights is not None else per_sample_weights
+        return run(ids.values, ids.row_splits, combiner, w)
+
+    if per_sample_weights is not None and combiner is None:
+        raise ValueError("per_sample_weights require a combiner "
+                         "('sum' or 'mean')")
+
+    if ids.layout == torch.sparse_coo:
+        if combiner is None:
+            raise ValueError("Sparse input requires a combiner ('sum' or 'mean')")
+        ids = ids.coalesce()
+        splits = row_to_split(ids.indices().t().contiguous(), ids.shape[0])
+        w = per_sample_weights
+        if w is not None:
+            if w.layout == torch.sparse_coo:
+                if w.shape != ids.shape:
+                    raise ValueError(f"sparse weights shape {tuple(w.shape)} does "
+                                     f"not match ids shape {tuple(ids.shape)}")
+                w = w.coalesce().values()
+            elif w.dim() != 1:
+                raise ValueError("weights for sparse ids must be sparse COO or "
+                                 "1-D, aligned with the coalesced values")
+        return run(ids.values(), splits, combiner, w)
+
+    if combiner is None:
+        flat = ids.reshape(-1)
+        splits = torch.arange(flat.numel() + 1, device=flat.device,
+                              dtype=torch.long)
+        return run(flat, splits, "sum").view(*ids.shape, width)
+
+    if ids.dim() != 2:
+        raise ValueError(f"Dense ids with combiner must be 2-D, got {ids.dim()}-D")
+    if per_sample_weights is not None and per_sample_weights.shape != ids.shape:
+        raise ValueError(
+            f"per_sample_weights shape {tuple(per_sample_weights.shape)} "
+            f"does not match ids shape {tuple(ids.shape)}")
+    b, h = ids.shape
+    splits = torch.arange(b + 1, device=ids.device, dtype=torch.long) * h
+    return run(ids.reshape(-1), splits, combiner, per_sample_weights)

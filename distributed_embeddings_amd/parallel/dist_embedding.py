@@ -32,7 +32,8 @@ import torch
 from torch import nn
 
 from ..layers.embedding import Embedding
-from ..ops.embedding_lookup import Ragged, embedding_lookup
+from ..ops.embedding_lookup import (Ragged, embedding_lookup,
+                                    quantized_embedding_lookup)
 from . import comm
 from .strategy import DistEmbeddingStrategy, TableConfig
 
@@ -96,6 +97,13 @@ def _layer_weight(obj, rows, cols):
     return None
 
 
+def _offloaded_lookup(layer, ragged, combiner):
+    """Lookup from a CPU-offloaded table, quantized or not."""
+    if layer.quantized:
+        return quantized_embedding_lookup(layer.qweight, ragged, combiner)
+    return embedding_lookup(layer.weight, ragged, combiner)
+
+
 class DistributedEmbedding(nn.Module):
     """Shards a list of embedding tables across all ranks of the default group.
 
@@ -150,6 +158,7 @@ class DistributedEmbedding(nn.Module):
         )
         self._built = False
         self._local_batch = None
+        self.quantized = False
 
         plan = self.strategy
         # ---- data-parallel layers (replicated; grads allreduced) ----
@@ -265,6 +274,36 @@ class DistributedEmbedding(nn.Module):
             lyr.enable_fused_optimizer(method, lr, eps)
         return self
 
+    def quantize_(self, chunk_rows: int = 1 << 20):
+        """Converts every local table to int8 row-wise storage for serving
+        (``Embedding.quantize_``): data-parallel tables, fused column-slice
+        groups, row shards and CPU-offloaded tables, each on its device.
+        Order of use: load the weights, quantize, serve.  Afterwards
+        ``forward`` / ``forward_packed`` run the quantized lookups, outputs
+        carry no grad, and ``get_weights`` / ``set_weights`` and the
+        checkpoint helpers raise.
+
+        Each local table is quantized by itself, so a column-sliced table
+        gets one scale and bias per row *per slice*: slightly more accurate
+        than quantizing the whole row, but not the same bytes."""
+        layers = (list(self.dp_layers) + list(self.col_layers)
+                  + list(self.row_layers))
+        # all or nothing: refuse before the first table is converted
+        if any(getattr(lyr, "_fused_lr", None) is not None
+               and not lyr.quantized for lyr in layers):
+            raise RuntimeError("tables with a fused optimizer enabled cannot "
+                               "be quantized: they are being trained")
+        for lyr in layers:
+            lyr.quantize_(chunk_rows)
+        self.quantized = True
+        return self
+
+    def _check_not_quantized(self, what):
+        if self.quantized:
+            raise RuntimeError(
+                f"{what} is not available on quantized (int8) tables: load "
+                "the weights first, then quantize_(), then serve")
+
     def set_fused_lr(self, lr: float):
         for lyr in list(self.col_layers) + list(self.row_layers):
             if getattr(lyr, "_fused_lr", None) is not None:
@@ -364,6 +403,7 @@ class DistributedEmbedding(nn.Module):
         table order — the checkpoint layout contract of the reference
         (``set_weights`` :971-1022; chunked writes parity :1003-1017).
         """
+        self._check_not_quantized("set_weights")
         cfgs = self.strategy.configs
         if len(weights) != len(cfgs):
             raise ValueError(f"expected {len(cfgs)} tables, got {len(weights)}")
@@ -406,6 +446,7 @@ class DistributedEmbedding(nn.Module):
         construction).
         """
         import torch.distributed as dist
+        self._check_not_quantized("get_weights")
         cfgs = self.strategy.configs
         plan = self.strategy
         out: List[Optional[np.ndarray]] = [None] * len(cfgs)
@@ -470,8 +511,10 @@ class DistributedEmbedding(nn.Module):
         if self.world_size > 1 and dist.get_backend() == "nccl":
             return torch.device("cuda", torch.cuda.current_device())
         if self.world_size == 1:
-            return self.col_layers[0].weight.device if len(self.col_layers) else \
-                torch.device("cpu")
+            if not len(self.col_layers):
+                return torch.device("cpu")
+            lyr = self.col_layers[0]
+            return (lyr.qweight if lyr.quantized else lyr.weight).device
         return torch.device("cpu")
 
     # ----------------------------------------------------- table parallel path
@@ -699,8 +742,8 @@ class DistributedEmbedding(nn.Module):
                 if offload:
                     allids_cpu = allids.cpu()
                     splits = torch.arange(allids_cpu.numel() + 1, dtype=torch.long)
-                    emb = embedding_lookup(layer.weight, Ragged(allids_cpu, splits),
-                                           "sum").to(allids.device)
+                    emb = _offloaded_lookup(layer, Ragged(allids_cpu, splits),
+                                            "sum").to(allids.device)
                 else:
                     splits = torch.arange(allids.numel() + 1, device=allids.device,
                                           dtype=torch.long)
@@ -792,8 +835,8 @@ class DistributedEmbedding(nn.Module):
                                             device=device)
                     torch.cumsum(all_lengths, 0, out=allsplits[1:])
                 if offload:
-                    out = embedding_lookup(
-                        layer.weight,
+                    out = _offloaded_lookup(
+                        layer,
                         Ragged(allvals.cpu(), allsplits.cpu(),
                                None if allw is None else allw.cpu()),
                         grp.combiner).to(allvals.device)

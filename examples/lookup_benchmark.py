@@ -4,6 +4,9 @@ step vs the plain-PyTorch equivalent.
 
 Capability parity with the reference ``examples/benchmarks/benchmark.py:23-98``
 (voc=1e6, width=128, batch=16384, hotness<=500).
+
+``--table-dtype int8`` times the forward only, from an int8 row-wise quantized
+table next to the fp32 one it was made from (quantized tables do not train).
 """
 
 import argparse
@@ -39,6 +42,9 @@ def main():
     p.add_argument("--max-hotness", type=int, default=500)
     p.add_argument("--weighted", action="store_true",
                    help="also time the same shapes with random per-id weights")
+    p.add_argument("--table-dtype", default="fp32", choices=["fp32", "int8"],
+                   help="int8: forward-only measurement from the row-wise "
+                        "quantized table")
     args = p.parse_args()
     device = "cuda" if torch.cuda.is_available() else "cpu"
 
@@ -53,6 +59,15 @@ def main():
     opt = SparseEmbeddingOptimizer(emb.parameters(), lr=0.01)
 
     print(f"custom fwd           {timeit(lambda: emb(ragged)):8.3f} ms")
+
+    if args.table_dtype == "int8":
+        emb.quantize_()
+        print(f"int8 fwd             {timeit(lambda: emb(ragged)):8.3f} ms")
+        if args.weighted:
+            w = torch.rand(values.numel(), generator=g).to(device)
+            weighted = Ragged(ragged.values, ragged.row_splits, w)
+            print(f"int8 weighted fwd    {timeit(lambda: emb(weighted)):8.3f} ms")
+        return
 
     def fwd_bwd():
         opt.zero_grad()
