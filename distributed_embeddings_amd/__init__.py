@@ -11,7 +11,8 @@ Public API (parity: reference ``distributed_embeddings/__init__.py:17-27``):
 
 from .ops.embedding_lookup import (Ragged, dequantize_rowwise_int8,
                                    embedding_lookup, quantize_rowwise_int8,
-                                   quantized_embedding_lookup, row_to_split)
+                                   quantized_embedding_lookup, row_to_split,
+                                   stochastic_round_bf16)
 from .layers.embedding import ConcatOneHotEmbedding, Embedding, scaled_uniform_init
 from .layers.integer_lookup import IntegerLookup
 from .parallel.strategy import DistEmbeddingStrategy, TableConfig
@@ -37,6 +38,7 @@ __all__ = [
     "quantize_rowwise_int8",
     "dequantize_rowwise_int8",
     "quantized_embedding_lookup",
+    "stochastic_round_bf16",
     "Embedding",
     "IntegerLookup",
     "ConcatOneHotEmbedding",

@@ -578,15 +578,34 @@ static bool check_adagrad_state(const torch::Tensor& state,
   return rowwise;
 }
 
+// The {seed, step} pair of stochastic rounding: int64 [2] on the weight's
+// device, bf16 weights only.  Returns its pointer, nullptr without one.
+static int64_t* sr_ptr(const std::optional<torch::Tensor>& sr,
+                       const torch::Tensor& weight) {
+  if (!sr.has_value()) return nullptr;
+  const torch::Tensor& t = *sr;
+  CHECK_CUDA(t); CHECK_CONTIG(t);
+  TORCH_CHECK(t.dtype() == torch::kInt64 && t.dim() == 1 && t.numel() == 2,
+              "sr must be an int64 [2] tensor {seed, step}");
+  TORCH_CHECK(t.device() == weight.device(),
+              "sr must be on the weight's device");
+  TORCH_CHECK(weight.dtype() == torch::kBFloat16,
+              "stochastic rounding needs a bf16 weight: an fp32 weight has "
+              "nothing to round");
+  return t.data_ptr<int64_t>();
+}
+
 void sparse_row_update(torch::Tensor weight, torch::Tensor state,
                        torch::Tensor ids, torch::Tensor grad, double lr,
-                       double eps, bool adagrad) {
+                       double eps, bool adagrad,
+                       std::optional<torch::Tensor> sr) {
   CHECK_CUDA(weight); CHECK_CUDA(ids); CHECK_CUDA(grad);
   CHECK_CONTIG(weight); CHECK_CONTIG(ids); CHECK_CONTIG(grad);
   TORCH_CHECK(weight.dtype() == torch::kFloat32 ||
               weight.dtype() == torch::kBFloat16);
   TORCH_CHECK(grad.dtype() == torch::kFloat32);
   TORCH_CHECK(ids.dtype() == torch::kInt64);
+  int64_t* sr_p = sr_ptr(sr, weight);
   const int64_t n = ids.numel();
   if (n == 0) return;
   float* state_ptr = nullptr;
@@ -599,14 +618,15 @@ void sparse_row_update(torch::Tensor weight, torch::Tensor state,
                            weight.dtype() == torch::kBFloat16, state_ptr,
                            ids.data_ptr<int64_t>(), grad.data_ptr<float>(), n,
                            (int)weight.size(1), (float)lr, (float)eps, adagrad,
-                           rowwise, current_stream());
+                           rowwise, sr_p, current_stream());
 }
 
 void csr_fused_optimizer_apply(torch::Tensor weight, torch::Tensor state,
                                torch::Tensor values, torch::Tensor row_splits,
                                torch::Tensor grad_out, torch::Tensor lr,
                                bool mean, bool adagrad, double eps,
-                               std::optional<torch::Tensor> per_id_w) {
+                               std::optional<torch::Tensor> per_id_w,
+                               std::optional<torch::Tensor> sr) {
   // All-device sorted pipeline (no host sync; hipGraph-capturable):
   // sort (id, pos) -> permute row-ids -> head-flag unique -> segment pad ->
   // one direct update per unique row (long segments chunked with one atomic
@@ -622,6 +642,7 @@ void csr_fused_optimizer_apply(torch::Tensor weight, torch::Tensor state,
                grad_out.dtype() == torch::kBFloat16) &&
               lr.dtype() == torch::kFloat32);
   const float* user_w = per_id_w_ptr(per_id_w, values);
+  int64_t* sr_p = sr_ptr(sr, weight);
   const bool wbf16 = weight.dtype() == torch::kBFloat16;
   const int64_t num_rows = row_splits.numel() - 1;
   const int64_t nnz = values.numel();
@@ -668,7 +689,20 @@ void csr_fused_optimizer_apply(torch::Tensor weight, torch::Tensor state,
                                  long_count.data_ptr<int32_t>(),
                                  work_items.data_ptr<int64_t>(),
                                  n_work.data_ptr<int32_t>(), scratch_ptr,
-                                 scratch_rows, adagrad, rowwise, stream);
+                                 scratch_rows, adagrad, rowwise, sr_p, stream);
+}
+
+// fp32 [n] -> bf16 [n], stochastically rounded with the bits the fused
+// optimizers use for table offsets base_offset .. base_offset + n - 1.
+torch::Tensor stochastic_round_bf16(torch::Tensor x, int64_t seed,
+                                    int64_t step, int64_t base_offset) {
+  CHECK_CUDA(x); CHECK_CONTIG(x);
+  TORCH_CHECK(x.dtype() == torch::kFloat32, "x must be fp32");
+  TORCH_CHECK(base_offset >= 0, "base_offset must not be negative");
+  auto out = torch::empty(x.sizes(), x.options().dtype(torch::kBFloat16));
+  launch_stochastic_round_bf16(x.data_ptr<float>(), out.data_ptr(), x.numel(),
+                               seed, step, base_offset, current_stream());
+  return out;
 }
 
 torch::Tensor dot_interact_fwd(torch::Tensor feats, int64_t out_w) {
@@ -845,14 +879,22 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("integer_lookup", &integer_lookup,
         "open-addressing hash vocab build + lookup (gfx950)");
   m.def("sparse_row_update", &sparse_row_update,
-        "fused sparse SGD/Adagrad/row-wise Adagrad row update (gfx950)");
+        "fused sparse SGD/Adagrad/row-wise Adagrad row update (gfx950)",
+        pybind11::arg("weight"), pybind11::arg("state"), pybind11::arg("ids"),
+        pybind11::arg("grad"), pybind11::arg("lr"), pybind11::arg("eps"),
+        pybind11::arg("adagrad"), pybind11::arg("sr") = pybind11::none());
   m.def("csr_fused_optimizer_apply", &csr_fused_optimizer_apply,
         "in-backward fused SGD/Adagrad/row-wise Adagrad update (gfx950)",
         pybind11::arg("weight"), pybind11::arg("state"),
         pybind11::arg("values"), pybind11::arg("row_splits"),
         pybind11::arg("grad_out"), pybind11::arg("lr"), pybind11::arg("mean"),
         pybind11::arg("adagrad"), pybind11::arg("eps"),
-        pybind11::arg("per_id_w") = pybind11::none());
+        pybind11::arg("per_id_w") = pybind11::none(),
+        pybind11::arg("sr") = pybind11::none());
+  m.def("stochastic_round_bf16", &stochastic_round_bf16,
+        "fp32 -> bf16 with the fused optimizers' stochastic rounding (gfx950)",
+        pybind11::arg("x"), pybind11::arg("seed"), pybind11::arg("step") = 0,
+        pybind11::arg("base_offset") = 0);
   m.def("dot_interact_fwd_packed", &dot_interact_fwd_packed,
         "pairwise-dot interaction on (bottom, packed, perm) (MFMA, gfx950)");
   m.def("dot_interact_bwd_packed", &dot_interact_bwd_packed,

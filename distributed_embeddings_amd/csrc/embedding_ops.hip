@@ -25,8 +25,10 @@
 //     lookup (the forward's per_id_w): one lane group per id, no atomics.
 //   * csr_fused_optimizer_apply — the same pipeline with the SGD, Adagrad or
 //     row-wise Adagrad update applied in place (no host sync;
-//     hipGraph-capturable).
-//   * integer_lookup      — open-addressing (linear probe) int64 hash
+//     hipGraph-capturable).  bf16 tables can take the update with stochastic
+//     rounding: counter-based bits per table element, step counter on the
+//     device (stochastic_round_bf16 is the same rounding as an op).
+//   * integer_lookup     — open-addressing (linear probe) int64 hash
 //     resident in torch buffers; two-kernel design (free-slot scan, then
 //     insert_and_find with device-scope 64-bit atomicCAS) replacing the
 //     reference's cooperative cuCollections kernel (K8-K9 equivalent).
@@ -120,6 +122,132 @@ __device__ __forceinline__ void pt_storev(T* p, const float* v) {
   if constexpr (VEC == 4) pt_store4(p, v);
   else if constexpr (VEC == 2) pt_store2(p, v);
   else pt_store(p, v[0]);
+}
+
+// ---------------------------------------------------------------------------
+// Stochastic rounding of fp32 to bf16 (optimizer writes to bf16 tables only).
+//
+// A finite x with bit pattern u and 16 random bits r is stored as
+// (u + r) >> 16: away from zero with probability low16(u) / 65536, unbiased,
+// and a bf16-representable x never moves.  Above the largest finite bf16 the
+// result may be +-inf, as with RNE.  Inf and NaN take the RNE path: adding r
+// to a NaN payload can carry into the sign bit.
+//
+// r is a function of (seed, step, o) alone, o = row * width + col being the
+// element's offset in the local table -- not of the thread, tile or kernel:
+//   key = mix64(seed ^ mix64(step))
+//   h   = mix64(key + (o >> 2))
+//   r   = (h >> (16 * (o & 3))) & 0xFFFF
+// so one 64-bit hash serves an aligned group of four elements.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ uint64_t mix64(uint64_t k) {
+  // splitmix64 finalizer
+  k += 0x9E3779B97F4A7C15ull;
+  k = (k ^ (k >> 30)) * 0xBF58476D1CE4E5B9ull;
+  k = (k ^ (k >> 27)) * 0x94D049BB133111EBull;
+  return k ^ (k >> 31);
+}
+
+__device__ __forceinline__ uint64_t sr_key(uint64_t seed, uint64_t step) {
+  return mix64(seed ^ mix64(step));
+}
+// the 64 bits shared by the four elements o & ~3 .. o | 3
+__device__ __forceinline__ uint64_t sr_hash(uint64_t key, int64_t o) {
+  return mix64(key + ((uint64_t)o >> 2));
+}
+__device__ __forceinline__ unsigned int sr_pick(uint64_t h, int64_t o) {
+  return (unsigned int)(h >> (16 * (int)(o & 3))) & 0xFFFFu;
+}
+__device__ __forceinline__ unsigned int sr_bits(uint64_t seed, uint64_t step,
+                                                int64_t o) {
+  return sr_pick(sr_hash(sr_key(seed, step), o), o);
+}
+
+__device__ __forceinline__ unsigned short bf16_rne_bits(float v) {
+  __hip_bfloat16 h(v);
+  return *reinterpret_cast<unsigned short*>(&h);
+}
+__device__ __forceinline__ unsigned short bf16_sr_bits(float v,
+                                                       unsigned int r) {
+  union { float f; unsigned int u; } c;
+  c.f = v;
+  if ((c.u & 0x7F800000u) == 0x7F800000u) return bf16_rne_bits(v);
+  return (unsigned short)((c.u + r) >> 16);  // finite: no carry past bit 31
+}
+
+// What a kernel keeps of the {seed, step} pair.  Rounding is a template flag
+// of the update kernels (SR, instantiated for bf16 tables only): `on` is a
+// compile-time constant after inlining, so an SR = false kernel is the
+// nearest-even kernel, instruction for instruction, and reads no pair.
+struct SrState {
+  uint64_t key;
+  bool on;
+};
+template <bool SR>
+__device__ __forceinline__ SrState sr_load(const int64_t* __restrict__ sr) {
+  if constexpr (SR) return {sr_key((uint64_t)sr[0], (uint64_t)sr[1]), true};
+  else return {0, false};
+}
+
+// The hash of o's group of four when rounding is on (0 otherwise), for
+// callers that store several elements of one group.
+__device__ __forceinline__ uint64_t sr_group_hash(SrState sr, int64_t o) {
+  return sr.on ? sr_hash(sr.key, o) : 0;
+}
+
+// Optimizer stores: element o of the table gets v.  fp32 stores v; bf16
+// rounds stochastically when sr.on and to nearest-even otherwise.  The
+// scalar store takes h = sr_group_hash(sr, o).
+__device__ __forceinline__ void pt_store_sr(float* p, float v, SrState,
+                                            uint64_t, int64_t) {
+  *p = v;
+}
+__device__ __forceinline__ void pt_store_sr(bf16_t* p, float v, SrState sr,
+                                            uint64_t h, int64_t o) {
+  p->b = sr.on ? bf16_sr_bits(v, sr_pick(h, o)) : bf16_rne_bits(v);
+}
+// o is a multiple of 2: both elements share one hash
+__device__ __forceinline__ void pt_store2_sr(float* p, const float* v, SrState,
+                                             int64_t) {
+  pt_store2(p, v);
+}
+__device__ __forceinline__ void pt_store2_sr(bf16_t* p, const float* v,
+                                             SrState sr, int64_t o) {
+  if (!sr.on) {
+    pt_store2(p, v);
+    return;
+  }
+  const uint64_t h = sr_hash(sr.key, o);
+  short2 s;
+  s.x = (short)bf16_sr_bits(v[0], sr_pick(h, o));
+  s.y = (short)bf16_sr_bits(v[1], sr_pick(h, o + 1));
+  *reinterpret_cast<short2*>(p) = s;
+}
+// o is a multiple of 4: the hash's four 16-bit fields in order
+__device__ __forceinline__ void pt_store4_sr(float* p, const float* v, SrState,
+                                             int64_t) {
+  pt_store4(p, v);
+}
+__device__ __forceinline__ void pt_store4_sr(bf16_t* p, const float* v,
+                                             SrState sr, int64_t o) {
+  if (!sr.on) {
+    pt_store4(p, v);
+    return;
+  }
+  const uint64_t h = sr_hash(sr.key, o);
+  short4 s;
+  s.x = (short)bf16_sr_bits(v[0], (unsigned int)h & 0xFFFFu);
+  s.y = (short)bf16_sr_bits(v[1], (unsigned int)(h >> 16) & 0xFFFFu);
+  s.z = (short)bf16_sr_bits(v[2], (unsigned int)(h >> 32) & 0xFFFFu);
+  s.w = (short)bf16_sr_bits(v[3], (unsigned int)(h >> 48));
+  *reinterpret_cast<short4*>(p) = s;
+}
+template <int VEC, typename T>
+__device__ __forceinline__ void pt_storev_sr(T* p, const float* v, SrState sr,
+                                             int64_t o) {
+  if constexpr (VEC == 4) pt_store4_sr(p, v, sr, o);
+  else if constexpr (VEC == 2) pt_store2_sr(p, v, sr, o);
+  else pt_store_sr(p, v[0], sr, sr_group_hash(sr, o), o);
 }
 
 static inline int next_pow2(int v) {
@@ -320,16 +448,34 @@ __device__ __forceinline__ float narrow_reduce(
 }
 
 // SGD: w -= lr * g.   Adagrad: s += g^2; w -= lr * g / (sqrt(s) + eps).
+// The new value of a weight w (fp32) and, for Adagrad, the state update.
+template <bool ADAGRAD>
+__device__ __forceinline__ float row_update_value(float w, float* state,
+                                                  float g, float lr, float eps,
+                                                  bool rounding) {
+  if (ADAGRAD) {
+    // The nearest-even kernels contract this sum to one fma.  The rounding
+    // kernels ask for it by name: their wide VEC = 2 instantiation otherwise
+    // came out as a packed multiply and a packed add, and the state differed
+    // from the nearest-even run's in the last bit.  Rounding is to touch the
+    // weights only.
+    const float st = rounding ? __builtin_fmaf(g, g, *state) : *state + g * g;
+    *state = st;
+    return w - lr * g / (sqrtf(st) + eps);
+  }
+  return w - lr * g;
+}
+
+// w is element o of the table and h = sr_group_hash(sr, o): they pick the
+// stochastic-rounding bits of a bf16 store.
 template <bool ADAGRAD, typename PT>
 __device__ __forceinline__ void apply_row_update(PT* w, float* state, float g,
-                                                 float lr, float eps) {
-  if (ADAGRAD) {
-    const float st = *state + g * g;
-    *state = st;
-    pt_store(w, pt_load(w) - lr * g / (sqrtf(st) + eps));
-  } else {
-    pt_store(w, pt_load(w) - lr * g);
-  }
+                                                 float lr, float eps,
+                                                 SrState sr, uint64_t h,
+                                                 int64_t o) {
+  pt_store_sr(w,
+              row_update_value<ADAGRAD>(pt_load(w), state, g, lr, eps, sr.on),
+              sr, h, o);
 }
 
 // Row-wise Adagrad: one fp32 accumulator per row,
@@ -364,16 +510,20 @@ __device__ __forceinline__ float rowwise_denom(float* state, float ssq,
 // One wave applies one row whose summed gradient g[0..width) sits in memory
 // nobody writes during the kernel (the optimizer step's grad rows, the
 // finalize kernel's completed scratch rows): squares first, update second.
+// row0 is the table offset of w[0].
 template <typename PT>
 __device__ __forceinline__ void rowwise_wave_update(
     PT* __restrict__ w, float* __restrict__ state, const float* __restrict__ g,
-    int width, int lane, float lr, float eps) {
+    int width, int lane, float lr, float eps, SrState sr, int64_t row0) {
   float ssq = 0.f;
   for (int c = lane; c < width; c += WAVE) ssq += g[c] * g[c];
   ssq = tile_sum(ssq, WAVE);
   const float denom = rowwise_denom(state, ssq, width, lane, WAVE, true, eps);
-  for (int c = lane; c < width; c += WAVE)
-    pt_store(&w[c], pt_load(&w[c]) - lr * g[c] / denom);
+  for (int c = lane; c < width; c += WAVE) {
+    const int64_t o = row0 + c;
+    pt_store_sr(&w[c], pt_load(&w[c]) - lr * g[c] / denom, sr,
+                sr_group_hash(sr, o), o);
+  }
 }
 
 // ---------------------------------------------------------------------------
@@ -604,6 +754,14 @@ template <typename F>
 static void dispatch_bool(bool b, F&& f) {
   if (b) f(std::true_type{});
   else f(std::false_type{});
+}
+
+// Calls f(std::true_type) for a bf16 table with a {seed, step} pair and
+// f(std::false_type) otherwise: fp32 tables get no rounding instantiation.
+template <typename PT, typename F>
+static void dispatch_sr(const int64_t* sr, F&& f) {
+  if constexpr (std::is_same<PT, float>::value) f(std::false_type{});
+  else dispatch_bool(sr != nullptr, f);
 }
 
 // Storage type selected by a dispatch_bool tag.
@@ -1174,7 +1332,7 @@ void launch_pad_seg_offsets(int64_t* seg, int64_t n, const int32_t* num_unique,
 // direct (non-atomic) update.  Grid-strides only over the REAL segment count
 // (*nu_ptr), not the padded nnz-sized buffer.  srow comes from our own
 // expansion, so the gathers need no bounds check.
-template <int TILE, int VEC, bool HAS_W, bool ADAGRAD, typename PT,
+template <int TILE, int VEC, bool HAS_W, bool ADAGRAD, bool SR, typename PT,
           typename GT>
 __global__ void sorted_opt_update(PT* __restrict__ weight,
                                   float* __restrict__ state, float eps,
@@ -1188,11 +1346,13 @@ __global__ void sorted_opt_update(PT* __restrict__ weight,
                                   int64_t long_thresh, int width,
                                   int64_t* __restrict__ long_rows,
                                   int32_t* __restrict__ long_count,
-                                  int tile_w) {
+                                  int tile_w,
+                                  const int64_t* __restrict__ sr_ptr) {
   const WaveCoord wc = wave_coord();
   const TileCoord tc = tile_coord(wc.lane, TILE > 0 ? WAVE : tile_w);
   const float lr = *lr_ptr;
   const int64_t n_segs = *nu_ptr;
+  const SrState sr = sr_load<SR>(sr_ptr);
   for (int64_t rbase = wc.wave_id * tc.rpw; rbase < n_segs;
        rbase += wc.n_waves * tc.rpw) {
     const int64_t r = rbase + tc.sub;
@@ -1210,18 +1370,37 @@ __global__ void sorted_opt_update(PT* __restrict__ weight,
       if (wc.lane < TILE && wc.lane < width) {
         const int64_t o = row0 + wc.lane;
         apply_row_update<ADAGRAD>(&weight[o], ADAGRAD ? &state[o] : nullptr, g,
-                                  lr, eps);
+                                  lr, eps, sr, sr_group_hash(sr, o), o);
       }
     } else {
       for (int col0 = tc.tl * VEC; col0 < width; col0 += tile_w * VEC) {
         float acc[VEC];
         wide_accumulate<VEC, HAS_W, false>(grad_out, srow, sw, 0, width, col0,
                                            s, e, acc);
+        // VEC divides width and col0, so o0 is a multiple of VEC and its
+        // VEC elements sit in one group of four: one hash for all
+        const int64_t o0 = row0 + col0;
+        if constexpr (SR) {
+          // One vector load and store per group.  The compiler makes these
+          // of the nearest-even path's per-element ones, but not once each
+          // store branches on finite / non-finite (measured: +24% on SGD,
+          // +50% on Adagrad with four 2-byte loads and stores per lane).
+          float wv[VEC];
+          pt_loadv<VEC>(weight + o0, wv);
 #pragma unroll
-        for (int v = 0; v < VEC; ++v) {
-          const int64_t o = row0 + col0 + v;
-          apply_row_update<ADAGRAD>(&weight[o], ADAGRAD ? &state[o] : nullptr,
-                                    acc[v], lr, eps);
+          for (int v = 0; v < VEC; ++v)
+            wv[v] = row_update_value<ADAGRAD>(
+                wv[v], ADAGRAD ? &state[o0 + v] : nullptr, acc[v], lr, eps,
+                true);
+          pt_storev_sr<VEC>(weight + o0, wv, sr, o0);
+        } else {
+#pragma unroll
+          for (int v = 0; v < VEC; ++v) {
+            const int64_t o = o0 + v;
+            apply_row_update<ADAGRAD>(&weight[o],
+                                      ADAGRAD ? &state[o] : nullptr, acc[v],
+                                      lr, eps, sr, 0, o);
+          }
         }
       }
     }
@@ -1236,7 +1415,7 @@ __global__ void sorted_opt_update(PT* __restrict__ weight,
 // column loops have wave-uniform trip counts, and a wide group with nothing
 // to do stays in step with live == false, because the lanes of one wave
 // shuffle together.
-template <int TILE, int VEC, bool HAS_W, typename PT, typename GT>
+template <int TILE, int VEC, bool HAS_W, bool SR, typename PT, typename GT>
 __global__ void sorted_opt_update_rowwise(
     PT* __restrict__ weight, float* __restrict__ state, float eps,
     const int64_t* __restrict__ sorted_ids, const int64_t* __restrict__ seg,
@@ -1244,11 +1423,12 @@ __global__ void sorted_opt_update_rowwise(
     const GT* __restrict__ grad_out, const float* __restrict__ lr_ptr,
     const int32_t* __restrict__ nu_ptr, int64_t long_thresh, int width,
     int64_t* __restrict__ long_rows, int32_t* __restrict__ long_count,
-    int tile_w) {
+    int tile_w, const int64_t* __restrict__ sr_ptr) {
   const WaveCoord wc = wave_coord();
   const TileCoord tc = tile_coord(wc.lane, TILE > 0 ? WAVE : tile_w);
   const float lr = *lr_ptr;
   const int64_t n_segs = *nu_ptr;
+  const SrState sr = sr_load<SR>(sr_ptr);
   for (int64_t rbase = wc.wave_id * tc.rpw; rbase < n_segs;
        rbase += wc.n_waves * tc.rpw) {
     const int64_t r = rbase + tc.sub;
@@ -1273,8 +1453,11 @@ __global__ void sorted_opt_update_rowwise(
       const float ssq = tile_sum(mine ? g * g : 0.f, WAVE);
       const float denom =
           rowwise_denom(&state[uid], ssq, width, wc.lane, WAVE, true, eps);
-      if (mine)
-        pt_store(&wrow[wc.lane], pt_load(&wrow[wc.lane]) - lr * g / denom);
+      if (mine) {
+        const int64_t o = uid * (int64_t)width + wc.lane;
+        pt_store_sr(&wrow[wc.lane], pt_load(&wrow[wc.lane]) - lr * g / denom,
+                    sr, sr_group_hash(sr, o), o);
+      }
     } else {
       const int pass_w = tile_w * VEC;
       const int n_pass = (width + pass_w - 1) / pass_w;
@@ -1304,7 +1487,8 @@ __global__ void sorted_opt_update_rowwise(
           pt_loadv<VEC>(wrow + col0, wv);
 #pragma unroll
           for (int v = 0; v < VEC; ++v) wv[v] -= lr * acc[v] / denom;
-          pt_storev<VEC>(wrow + col0, wv);
+          pt_storev_sr<VEC>(wrow + col0, wv, sr,
+                            uid * (int64_t)width + col0);
         }
       }
     }
@@ -1355,52 +1539,64 @@ __global__ void sorted_opt_long(float* __restrict__ target,  // weight or scratc
   }
 }
 
-template <bool ADAGRAD, typename PT>
+template <bool ADAGRAD, bool SR, typename PT>
 __global__ void sorted_long_finalize(
     PT* __restrict__ weight, float* __restrict__ state, float eps,
     const int64_t* __restrict__ sorted_ids, const int64_t* __restrict__ seg,
     const float* __restrict__ lr_ptr, int width,
     const int64_t* __restrict__ long_rows,
-    const int32_t* __restrict__ long_count, const float* __restrict__ scratch) {
+    const int32_t* __restrict__ long_count, const float* __restrict__ scratch,
+    const int64_t* __restrict__ sr_ptr) {
   const WaveCoord wc = wave_coord();
   const float lr = *lr_ptr;
   const int64_t n_long = *long_count;
+  const SrState sr = sr_load<SR>(sr_ptr);
   for (int64_t li = wc.wave_id; li < n_long; li += wc.n_waves) {
     const int64_t uid = sorted_ids[seg[long_rows[li]]];
     for (int c = wc.lane; c < width; c += WAVE) {
       const int64_t o = uid * (int64_t)width + c;
       apply_row_update<ADAGRAD>(&weight[o], ADAGRAD ? &state[o] : nullptr,
-                                scratch[li * (int64_t)width + c], lr, eps);
+                                scratch[li * (int64_t)width + c], lr, eps, sr,
+                                sr_group_hash(sr, o), o);
     }
   }
 }
 
 // Row-wise Adagrad finalize: the chunk kernel has completed the scratch row.
-template <typename PT>
+template <bool SR, typename PT>
 __global__ void sorted_long_finalize_rowwise(
     PT* __restrict__ weight, float* __restrict__ state, float eps,
     const int64_t* __restrict__ sorted_ids, const int64_t* __restrict__ seg,
     const float* __restrict__ lr_ptr, int width,
     const int64_t* __restrict__ long_rows,
-    const int32_t* __restrict__ long_count, const float* __restrict__ scratch) {
+    const int32_t* __restrict__ long_count, const float* __restrict__ scratch,
+    const int64_t* __restrict__ sr_ptr) {
   const WaveCoord wc = wave_coord();
   const float lr = *lr_ptr;
   const int64_t n_long = *long_count;
+  const SrState sr = sr_load<SR>(sr_ptr);
   for (int64_t li = wc.wave_id; li < n_long; li += wc.n_waves) {
     const int64_t uid = sorted_ids[seg[long_rows[li]]];
     rowwise_wave_update(weight + uid * (int64_t)width, &state[uid],
-                        scratch + li * (int64_t)width, width, wc.lane, lr, eps);
+                        scratch + li * (int64_t)width, width, wc.lane, lr, eps,
+                        sr, uid * (int64_t)width);
   }
 }
 
-template <typename PT, typename GT>
+// Ends an apply that rounded stochastically: every kernel before it on the
+// stream has read sr[1], the next apply (or graph replay) reads the new one.
+__global__ void sr_advance_step(int64_t* __restrict__ sr) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) sr[1] = sr[1] + 1;
+}
+
+template <bool SR, typename PT, typename GT>
 static void launch_sorted_optimizer_update_t(
     PT* weight, float* state, float eps, const int64_t* sorted_ids,
     const int64_t* seg, const int64_t* srow, const float* sw,
     const GT* grad_out, const float* lr, const int32_t* nu_ptr,
     int64_t max_segs, int width, int64_t* long_rows, int32_t* long_count,
     int64_t* work_items, int32_t* n_work, float* long_scratch, bool adagrad,
-    bool rowwise, hipStream_t stream) {
+    bool rowwise, const int64_t* sr, hipStream_t stream) {
   const dim3 block(256);
   // bf16 weights have no atomicAdd: their long-SGD path also goes through the
   // fp32 scratch + finalize pair.
@@ -1413,18 +1609,18 @@ static void launch_sorted_optimizer_update_t(
       constexpr bool HAS_W = decltype(has_w_t)::value;
       if (rowwise) {
         hipLaunchKernelGGL(
-            (sorted_opt_update_rowwise<TILE, VEC, HAS_W, PT, GT>), grid, block,
-            0, stream, weight, state, eps, sorted_ids, seg, srow, sw, grad_out,
-            lr, nu_ptr, (int64_t)LONG_T, width, long_rows, long_count,
-            t.tile_w);
+            (sorted_opt_update_rowwise<TILE, VEC, HAS_W, SR, PT, GT>), grid,
+            block, 0, stream, weight, state, eps, sorted_ids, seg, srow, sw,
+            grad_out, lr, nu_ptr, (int64_t)LONG_T, width, long_rows,
+            long_count, t.tile_w, sr);
       } else {
         dispatch_bool(adagrad, [&](auto ada) {
           hipLaunchKernelGGL(
-              (sorted_opt_update<TILE, VEC, HAS_W, decltype(ada)::value, PT,
-                                 GT>),
+              (sorted_opt_update<TILE, VEC, HAS_W, decltype(ada)::value, SR,
+                                 PT, GT>),
               grid, block, 0, stream, weight, state, eps, sorted_ids, seg,
               srow, sw, grad_out, lr, nu_ptr, (int64_t)LONG_T, width,
-              long_rows, long_count, t.tile_w);
+              long_rows, long_count, t.tile_w, sr);
         });
       }
       hipLaunchKernelGGL(expand_long_work, dim3(512), block, 0, stream,
@@ -1439,15 +1635,15 @@ static void launch_sorted_optimizer_update_t(
       });
     });
     if (rowwise)
-      hipLaunchKernelGGL((sorted_long_finalize_rowwise<PT>), dim3(256), block,
-                         0, stream, weight, state, eps, sorted_ids, seg, lr,
-                         width, long_rows, long_count, long_scratch);
+      hipLaunchKernelGGL((sorted_long_finalize_rowwise<SR, PT>), dim3(256),
+                         block, 0, stream, weight, state, eps, sorted_ids, seg,
+                         lr, width, long_rows, long_count, long_scratch, sr);
     else if (use_scratch)
       dispatch_bool(adagrad, [&](auto ada) {
-        hipLaunchKernelGGL((sorted_long_finalize<decltype(ada)::value, PT>),
-                           dim3(256), block, 0, stream, weight, state, eps,
-                           sorted_ids, seg, lr, width, long_rows, long_count,
-                           long_scratch);
+        hipLaunchKernelGGL(
+            (sorted_long_finalize<decltype(ada)::value, SR, PT>), dim3(256),
+            block, 0, stream, weight, state, eps, sorted_ids, seg, lr, width,
+            long_rows, long_count, long_scratch, sr);
       });
   });
 }
@@ -1463,8 +1659,9 @@ void launch_sorted_optimizer_update(void* weight, bool weight_bf16,
                                     int64_t* long_rows, int32_t* long_count,
                                     int64_t* work_items, int32_t* n_work,
                                     float* long_scratch, int64_t scratch_rows,
-                                    bool adagrad, bool rowwise,
+                                    bool adagrad, bool rowwise, int64_t* sr,
                                     hipStream_t stream) {
+  if (!weight_bf16) sr = nullptr;  // fp32 tables do not round
   hipMemsetAsync(long_count, 0, sizeof(int32_t), stream);
   hipMemsetAsync(n_work, 0, sizeof(int32_t), stream);
   if (long_scratch) {
@@ -1475,13 +1672,17 @@ void launch_sorted_optimizer_update(void* weight, bool weight_bf16,
     dispatch_bool(grad_bf16, [&](auto g_bf16) {
       using PT = storage_t<decltype(w_bf16)>;
       using GT = storage_t<decltype(g_bf16)>;
-      launch_sorted_optimizer_update_t(
-          (PT*)weight, state, eps, sorted_ids, seg, srow, sw,
-          (const GT*)grad_out, lr, nu_ptr, max_segs, width, long_rows,
-          long_count, work_items, n_work, long_scratch, adagrad, rowwise,
-          stream);
+      dispatch_sr<PT>(sr, [&](auto sr_t) {
+        launch_sorted_optimizer_update_t<decltype(sr_t)::value>(
+            (PT*)weight, state, eps, sorted_ids, seg, srow, sw,
+            (const GT*)grad_out, lr, nu_ptr, max_segs, width, long_rows,
+            long_count, work_items, n_work, long_scratch, adagrad, rowwise,
+            sr, stream);
+      });
     });
   });
+  if (sr)
+    hipLaunchKernelGGL(sr_advance_step, dim3(1), dim3(WAVE), 0, stream, sr);
 }
 
 // ---------------------------------------------------------------------------
@@ -1580,73 +1781,109 @@ void launch_csr_weight_grad(const void* params, bool params_bf16,
 // One wave per row.
 // ---------------------------------------------------------------------------
 
-template <bool ADAGRAD, typename PT>
+template <bool ADAGRAD, bool SR, typename PT>
 __global__ void sparse_row_update(PT* __restrict__ weight,
                                   float* __restrict__ state,
                                   const int64_t* __restrict__ ids,
                                   const float* __restrict__ grad,
                                   int64_t num_rows, int width, float lr,
-                                  float eps) {
+                                  float eps,
+                                  const int64_t* __restrict__ sr_ptr) {
   const WaveCoord wc = wave_coord();
+  const SrState sr = sr_load<SR>(sr_ptr);
   for (int64_t r = wc.wave_id; r < num_rows; r += wc.n_waves) {
     const int64_t row0 = ids[r] * (int64_t)width;
     for (int c = wc.lane; c < width; c += WAVE) {
       const int64_t o = row0 + c;
       apply_row_update<ADAGRAD>(&weight[o], ADAGRAD ? &state[o] : nullptr,
-                                grad[r * (int64_t)width + c], lr, eps);
+                                grad[r * (int64_t)width + c], lr, eps, sr,
+                                sr_group_hash(sr, o), o);
     }
   }
 }
 
 // Row-wise Adagrad: state is [vocab], one float per row.
-template <typename PT>
+template <bool SR, typename PT>
 __global__ void sparse_row_update_rowwise(PT* __restrict__ weight,
                                           float* __restrict__ state,
                                           const int64_t* __restrict__ ids,
                                           const float* __restrict__ grad,
                                           int64_t num_rows, int width,
-                                          float lr, float eps) {
+                                          float lr, float eps,
+                                          const int64_t* __restrict__ sr_ptr) {
   const WaveCoord wc = wave_coord();
+  const SrState sr = sr_load<SR>(sr_ptr);
   for (int64_t r = wc.wave_id; r < num_rows; r += wc.n_waves) {
     const int64_t uid = ids[r];
     rowwise_wave_update(weight + uid * (int64_t)width, &state[uid],
-                        grad + r * (int64_t)width, width, wc.lane, lr, eps);
+                        grad + r * (int64_t)width, width, wc.lane, lr, eps, sr,
+                        uid * (int64_t)width);
   }
 }
 
 void launch_sparse_row_update(void* weight, bool weight_bf16, float* state,
                               const int64_t* ids, const float* grad,
                               int64_t num_rows, int width, float lr, float eps,
-                              bool adagrad, bool rowwise, hipStream_t stream) {
+                              bool adagrad, bool rowwise, int64_t* sr,
+                              hipStream_t stream) {
   const int block = 256;
   const int grid = pick_grid(num_rows, block / WAVE);
+  if (!weight_bf16) sr = nullptr;  // fp32 tables do not round
   dispatch_bool(weight_bf16, [&](auto w_bf16) {
     using PT = storage_t<decltype(w_bf16)>;
-    if (rowwise) {
-      hipLaunchKernelGGL((sparse_row_update_rowwise<PT>), dim3(grid),
-                         dim3(block), 0, stream, (PT*)weight, state, ids, grad,
-                         num_rows, width, lr, eps);
-      return;
-    }
-    dispatch_bool(adagrad, [&](auto ada) {
-      hipLaunchKernelGGL((sparse_row_update<decltype(ada)::value, PT>),
-                         dim3(grid), dim3(block), 0, stream, (PT*)weight,
-                         state, ids, grad, num_rows, width, lr, eps);
+    dispatch_sr<PT>(sr, [&](auto sr_t) {
+      constexpr bool SR = decltype(sr_t)::value;
+      if (rowwise) {
+        hipLaunchKernelGGL((sparse_row_update_rowwise<SR, PT>), dim3(grid),
+                           dim3(block), 0, stream, (PT*)weight, state, ids,
+                           grad, num_rows, width, lr, eps, sr);
+        return;
+      }
+      dispatch_bool(adagrad, [&](auto ada) {
+        hipLaunchKernelGGL((sparse_row_update<decltype(ada)::value, SR, PT>),
+                           dim3(grid), dim3(block), 0, stream, (PT*)weight,
+                           state, ids, grad, num_rows, width, lr, eps, sr);
+      });
     });
   });
+  if (sr)
+    hipLaunchKernelGGL(sr_advance_step, dim3(1), dim3(WAVE), 0, stream, sr);
+}
+
+// ---------------------------------------------------------------------------
+// Stand-alone stochastic rounding: out[i] = SR(x[i]) with the bits of table
+// offset base_offset + i.  Any n and any base_offset, so one hash per element.
+// ---------------------------------------------------------------------------
+__global__ void stochastic_round_bf16_kernel(const float* __restrict__ x,
+                                             bf16_t* __restrict__ out,
+                                             int64_t n, uint64_t seed,
+                                             uint64_t step,
+                                             int64_t base_offset) {
+  const uint64_t key = sr_key(seed, step);
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += stride) {
+    const int64_t o = base_offset + i;
+    out[i].b = bf16_sr_bits(x[i], sr_pick(sr_hash(key, o), o));
+  }
+}
+
+void launch_stochastic_round_bf16(const float* x, void* out, int64_t n,
+                                  int64_t seed, int64_t step,
+                                  int64_t base_offset, hipStream_t stream) {
+  if (n <= 0) return;
+  const int block = 256;
+  int64_t grid = cdiv64(n, block);
+  if (grid > 16384) grid = 16384;
+  hipLaunchKernelGGL(stochastic_round_bf16_kernel, dim3((int)grid),
+                     dim3(block), 0, stream, x, (bf16_t*)out, n,
+                     (uint64_t)seed, (uint64_t)step, base_offset);
 }
 
 // ---------------------------------------------------------------------------
 // IntegerLookup hash (open addressing, linear probe, device-scope atomics).
+// Slots come from mix64 (top of the file).
 // ---------------------------------------------------------------------------
-
-__device__ __forceinline__ uint64_t mix64(uint64_t k) {
-  // splitmix64 finalizer
-  k += 0x9E3779B97F4A7C15ull;
-  k = (k ^ (k >> 30)) * 0xBF58476D1CE4E5B9ull;
-  k = (k ^ (k >> 27)) * 0x94D049BB133111EBull;
-  return k ^ (k >> 31);
-}
 
 // Pass 1: free values (counts[v]==0) -> avail list, ascending via scanned pos.
 __global__ void mark_free_values(const int32_t* __restrict__ counts, int64_t n,

@@ -94,6 +94,11 @@ void launch_pad_seg_offsets(int64_t* seg, int64_t n, const int32_t* num_unique,
 
 // rowwise (row-wise Adagrad) takes state as [vocab] fp32, one float per row,
 // in place of Adagrad's [vocab, width]; it implies adagrad.
+// sr: device pointer to {seed, step}, or nullptr.  With a bf16 weight it
+// selects stochastic rounding of the weight stores; every kernel of the call
+// reads the same step and a trailing one-thread kernel adds 1 to it, which is
+// why the pointer is not const.  nullptr (and any fp32 weight) keeps
+// round-to-nearest-even and launches nothing extra.
 void launch_sorted_optimizer_update(void* weight, bool weight_bf16,
                                     float* state, float eps,
                                     const int64_t* sorted_ids,
@@ -105,13 +110,20 @@ void launch_sorted_optimizer_update(void* weight, bool weight_bf16,
                                     int64_t* long_rows, int32_t* long_count,
                                     int64_t* work_items, int32_t* n_work,
                                     float* long_scratch, int64_t scratch_rows,
-                                    bool adagrad, bool rowwise,
+                                    bool adagrad, bool rowwise, int64_t* sr,
                                     hipStream_t stream);
 
 void launch_sparse_row_update(void* weight, bool weight_bf16, float* state,
                               const int64_t* ids, const float* grad,
                               int64_t num_rows, int width, float lr, float eps,
-                              bool adagrad, bool rowwise, hipStream_t stream);
+                              bool adagrad, bool rowwise, int64_t* sr,
+                              hipStream_t stream);
+
+// out[i] = bf16 of x[i], stochastically rounded with the bits of table offset
+// base_offset + i at (seed, step); out is bf16 [n].
+void launch_stochastic_round_bf16(const float* x, void* out, int64_t n,
+                                  int64_t seed, int64_t step,
+                                  int64_t base_offset, hipStream_t stream);
 
 void launch_dot_interact_fwd_packed(const void* bottom, const void* packed,
                                     const int* perm, void* out, int64_t B,

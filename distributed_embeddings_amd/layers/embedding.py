@@ -20,7 +20,7 @@ from ..ops.embedding_lookup import (Ragged, _csr_lookup_q8,
                                     csr_lookup_fused_optimizer,
                                     dequantize_rowwise_int8, embedding_lookup,
                                     quantize_rowwise_int8,
-                                    quantized_embedding_lookup)
+                                    quantized_embedding_lookup, to_int64)
 
 
 def _default_init(weight: torch.Tensor) -> None:
@@ -188,7 +188,9 @@ class Embedding(nn.Module):
         """In-backward SGD (see enable_fused_optimizer)."""
         return self.enable_fused_optimizer("sgd", lr)
 
-    def enable_fused_optimizer(self, method: str, lr: float, eps: float = 1e-10):
+    def enable_fused_optimizer(self, method: str, lr: float, eps: float = 1e-10,
+                               stochastic_rounding: bool = False,
+                               seed: Optional[int] = None):
         """In-backward fused optimizer: the lookup's backward applies the
         update directly (no grad tensor, no host sync; the step becomes
         hipGraph-capturable).  The training optimizer must not also update
@@ -197,13 +199,27 @@ class Embedding(nn.Module):
         ``method`` is ``"sgd"``, ``"adagrad"`` (fp32 state
         ``[input_dim, output_dim]``) or ``"rowwise_adagrad"`` (fp32 state
         ``[input_dim]``: one accumulator per row, fed with the mean square of
-        the row's summed gradient).  Calling it again replaces the state."""
+        the row's summed gradient).  Calling it again replaces the state.
+
+        ``stochastic_rounding`` (bf16 tables only; ``ValueError`` on fp32)
+        stores the updated weights with stochastic instead of nearest-even
+        rounding, so updates below half a bf16 ulp of the weight survive on
+        average instead of being dropped (``ops.stochastic_round_bf16``).  It
+        registers the int64 buffer ``_fused_sr = (seed, step)``; the step
+        counts the applied updates on the device and the buffer is part of
+        ``state_dict``, so a resumed run continues the bit stream.
+        ``seed=None`` draws the seed from torch's default CPU generator
+        (``torch.manual_seed`` makes runs repeatable)."""
         if method not in ("sgd", "adagrad", "rowwise_adagrad"):
             raise ValueError(f"unknown fused optimizer {method!r}")
         if self.quantized:
             raise RuntimeError("a quantized (int8) table is inference-only: "
                                "it takes no optimizer")
-        for name in ("_fused_lr", "_fused_state"):  # allow re-configuring
+        if stochastic_rounding and self.weight.dtype != torch.bfloat16:
+            raise ValueError("stochastic_rounding needs a bf16 table: an "
+                             f"{self.weight.dtype} table has nothing to round")
+        # allow re-configuring
+        for name in ("_fused_lr", "_fused_state", "_fused_sr"):
             if name in self._buffers:
                 del self._buffers[name]
         self.register_buffer("_fused_lr",
@@ -226,6 +242,15 @@ class Embedding(nn.Module):
         # weight itself carries de_local when model-parallel)
         self._fused_state.de_local = getattr(self.weight, "de_local", False)
         self._fused_lr.de_local = False  # lr is global; broadcasting is fine
+        if stochastic_rounding:
+            if seed is None:
+                seed = int(torch.randint(0, 1 << 62, (1,)))
+            self.register_buffer("_fused_sr",
+                                 torch.tensor([to_int64(int(seed)), 0],
+                                              dtype=torch.int64,
+                                              device=self.weight.device))
+            # the bit stream belongs to the shard, like the optimizer state
+            self._fused_sr.de_local = self._fused_state.de_local
         return self
 
     def set_fused_lr(self, lr: float):
@@ -257,7 +282,8 @@ class Embedding(nn.Module):
             return csr_lookup_fused_optimizer(
                 self.weight, values, row_splits, combiner, self._fused_lr,
                 self._fused_state, self._fused_method != "sgd",
-                self._fused_eps, out_dtype, per_id_w)
+                self._fused_eps, out_dtype, per_id_w,
+                getattr(self, "_fused_sr", None))
         from ..ops.embedding_lookup import _CsrLookup
         return _CsrLookup.apply(self.weight, values, row_splits, combiner,
                                 out_dtype, per_id_w)

@@ -259,6 +259,130 @@ def _csr_lookup_backward_ref(grad_out, values, row_splits, vocab, combiner,
     return unique_ids, unique_grad
 
 
+# ---------------------------------------------------------------------------
+# Stochastic rounding of optimizer writes to bf16 tables
+# ---------------------------------------------------------------------------
+#
+# A finite fp32 x with bit pattern u is stored as the bf16 ``(u + r) >> 16``
+# with 16 random bits r: away from zero with probability low16(u) / 65536,
+# unbiased, and a bf16-representable x never moves.  A value above the largest
+# finite bf16 may become +-inf, as with round-to-nearest-even.  Inf and NaN
+# round to nearest-even.  r depends on (seed, step, o) alone, o being the
+# element's offset ``row * width + col`` in the local table:
+#
+#     key = mix64(seed ^ mix64(step))
+#     h   = mix64(key + (o >> 2))
+#     r   = (h >> (16 * (o & 3))) & 0xFFFF
+#
+# with mix64 the splitmix64 finalizer of csrc/embedding_ops.hip.  The numpy
+# code below is the definition the HIP kernels are tested against, bit for
+# bit, and the CPU path of the feature.
+
+_U64 = (1 << 64) - 1
+
+
+def mix64_int(k: int) -> int:
+    """``mix64`` of csrc/embedding_ops.hip on a Python int (mod 2**64)."""
+    k = (k + 0x9E3779B97F4A7C15) & _U64
+    k = ((k ^ (k >> 30)) * 0xBF58476D1CE4E5B9) & _U64
+    k = ((k ^ (k >> 27)) * 0x94D049BB133111EB) & _U64
+    return k ^ (k >> 31)
+
+
+def to_int64(k: int) -> int:
+    """The int64 with the bit pattern of ``k`` mod 2**64."""
+    k &= _U64
+    return k - (1 << 64) if k >> 63 else k
+
+
+def _mix64_np(k):
+    import numpy as np
+    with np.errstate(over="ignore"):
+        k = k + np.uint64(0x9E3779B97F4A7C15)
+        k = (k ^ (k >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        k = (k ^ (k >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+    return k ^ (k >> np.uint64(31))
+
+
+def stochastic_rounding_bits(seed: int, step: int,
+                             offsets: torch.Tensor) -> torch.Tensor:
+    """The 16 random bits r of each table offset, as int64 in [0, 65536)."""
+    import numpy as np
+    o = offsets.detach().cpu().to(torch.int64).contiguous().numpy()
+    o = o.astype(np.uint64)
+    key = np.uint64(mix64_int((int(seed) & _U64) ^ mix64_int(int(step) & _U64)))
+    with np.errstate(over="ignore"):
+        h = _mix64_np(key + (o >> np.uint64(2)))
+    r = (h >> (np.uint64(16) * (o & np.uint64(3)))) & np.uint64(0xFFFF)
+    return torch.from_numpy(r.astype(np.int64))
+
+
+def _stochastic_round_bf16_ref(x: torch.Tensor, seed: int, step: int,
+                               offsets: torch.Tensor) -> torch.Tensor:
+    """CPU reference: fp32 ``x`` -> bf16, element ``i`` rounded with the bits
+    of table offset ``offsets[i]`` (same shape as ``x``)."""
+    x = x.detach().to(torch.float32).contiguous()
+    r = stochastic_rounding_bits(seed, step, offsets.reshape(-1)).view(x.shape)
+    u = x.view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+    finite = (u & 0x7F800000) != 0x7F800000
+    # inf keeps its top half; NaN keeps it too, quieted (0x7fc00000 ->
+    # 0x7fc0, what the device conversion stores).  Done on the bits:
+    # torch's own CPU cast gives NaN two different encodings, depending on
+    # whether the element falls into a vectorized stretch.
+    is_nan = ~finite & ((u & 0x007FFFFF) != 0)
+    hi = torch.where(finite, (u + r) >> 16,
+                     (u >> 16) | torch.where(is_nan, 0x0040, 0))
+    hi = torch.where(hi >= 0x8000, hi - 0x10000, hi).to(torch.int16)
+    return hi.view(torch.bfloat16)
+
+
+def stochastic_round_bf16(x: torch.Tensor, seed: int, step: int = 0,
+                          base_offset: int = 0) -> torch.Tensor:
+    """fp32 ``x`` -> bf16 by the stochastic rounding the fused optimizers
+    apply to bf16 tables: element ``i`` of the flattened ``x`` gets the bits
+    of table offset ``base_offset + i`` at ``(seed, step)``.
+
+    A finite value goes to one of its two bf16 neighbours, away from zero
+    with probability ``low16(bits) / 65536`` (unbiased; a representable value
+    stays).  Inf and NaN round to nearest-even; a finite value above the
+    largest finite bf16 may become +-inf.  On the GPU this is a HIP kernel,
+    on the CPU the numpy reference of the same function.
+    """
+    if x.dtype != torch.float32:
+        raise ValueError("stochastic_round_bf16 takes an fp32 tensor")
+    if base_offset < 0:
+        raise ValueError("base_offset must not be negative")
+    seed, step = to_int64(int(seed)), to_int64(int(step))
+    if x.is_cuda:
+        return _backend.ops().stochastic_round_bf16(
+            x.detach().contiguous(), seed, step, int(base_offset))
+    offsets = torch.arange(x.numel(), dtype=torch.int64) + int(base_offset)
+    return _stochastic_round_bf16_ref(x, seed, step, offsets.view(x.shape))
+
+
+def _check_sr(sr, weight) -> None:
+    if sr is None:
+        return
+    if weight.dtype != torch.bfloat16:
+        raise ValueError("stochastic rounding needs a bf16 table: an fp32 "
+                         "table has nothing to round")
+    if (sr.dtype != torch.int64 or sr.shape != (2,)
+            or sr.device != weight.device):
+        raise ValueError("sr must be an int64 [2] tensor (seed, step) on the "
+                         "weight's device")
+
+
+def _write_rows_sr(weight, ids, new_rows, sr) -> None:
+    """CPU: writes fp32 ``new_rows`` over the bf16 ``weight[ids]`` (unique
+    ids), stochastically rounded at the rows' table offsets, and advances the
+    step ``sr[1]``."""
+    seed, step = (int(v) for v in sr.tolist())
+    width = weight.shape[1]
+    offsets = ids.unsqueeze(1) * width + torch.arange(width, dtype=torch.int64)
+    weight[ids] = _stochastic_round_bf16_ref(new_rows, seed, step, offsets)
+    sr[1] += 1
+
+
 class _CsrLookupFusedOptimizer(torch.autograd.Function):
     """CSR lookup whose backward applies the optimizer update in place.
 
@@ -274,14 +398,24 @@ class _CsrLookupFusedOptimizer(torch.autograd.Function):
 
     With ``per_id_w`` the gradient of the weights is taken from the table as
     the forward read it: it is computed before the update touches the table.
+
+    ``sr`` (optional, bf16 tables only): int64 ``[2]`` tensor ``(seed, step)``
+    on the weight's device.  The updated weights are then stored with
+    stochastic rounding (``stochastic_round_bf16`` at the elements' table
+    offsets) and every backward that applies an update adds 1 to ``sr[1]`` --
+    on the device, so a captured step draws fresh bits on every replay.
     """
 
     @staticmethod
     def forward(ctx, weight, values, row_splits, combiner, lr, state, adagrad,
-                eps, out_dtype=None, per_id_w=None):
+                eps, out_dtype=None, per_id_w=None, sr=None):
+        _check_sr(sr, weight)
         w32 = _kernel_weights(per_id_w)
         need_dw = per_id_w is not None and ctx.needs_input_grad[9]
         ctx.save_for_backward(weight, values, row_splits, lr, state, w32)
+        # an int64 counter the backward itself advances: kept off the saved
+        # tensors, whose version check would reject that
+        ctx.sr = sr
         ctx.combiner = combiner
         ctx.adagrad = adagrad
         ctx.eps = eps
@@ -296,6 +430,7 @@ class _CsrLookupFusedOptimizer(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_out):
         weight, values, row_splits, lr, state, w32 = ctx.saved_tensors
+        sr = ctx.sr
         grad_out = grad_out.contiguous()
         dw = None
         with torch.no_grad():
@@ -306,7 +441,7 @@ class _CsrLookupFusedOptimizer(torch.autograd.Function):
             if weight.is_cuda:
                 _backend.ops().csr_fused_optimizer_apply(
                     weight, state, values, row_splits, grad_out, lr,
-                    ctx.combiner == "mean", ctx.adagrad, ctx.eps, w32)
+                    ctx.combiner == "mean", ctx.adagrad, ctx.eps, w32, sr)
             else:
                 unique_ids, unique_grad = _csr_lookup_backward_ref(
                     grad_out.float(), values, row_splits, weight.shape[0],
@@ -320,13 +455,16 @@ class _CsrLookupFusedOptimizer(torch.autograd.Function):
                     denom = state.index_select(0, unique_ids).sqrt_().add_(ctx.eps)
                     if rowwise:
                         denom = denom.unsqueeze(1)
-                    weight.index_add_(
-                        0, unique_ids,
-                        (-lr_v * unique_grad / denom).to(weight.dtype))
+                    delta = -lr_v * unique_grad / denom
                 else:
-                    weight.index_add_(0, unique_ids,
-                                      (unique_grad * (-lr_v)).to(weight.dtype))
-        return (None,) * 9 + (dw,)
+                    delta = unique_grad * (-lr_v)
+                if sr is None:
+                    weight.index_add_(0, unique_ids, delta.to(weight.dtype))
+                elif values.numel() > 0 and row_splits.numel() > 1:
+                    # the kernels' condition for launching (and advancing)
+                    rows = weight.index_select(0, unique_ids).float() + delta
+                    _write_rows_sr(weight, unique_ids, rows, sr)
+        return (None,) * 9 + (dw, None)
 
 
 def csr_lookup_fused_sgd(weight, values, row_splits, combiner, lr,
@@ -338,10 +476,11 @@ def csr_lookup_fused_sgd(weight, values, row_splits, combiner, lr,
 
 
 def csr_lookup_fused_optimizer(weight, values, row_splits, combiner, lr, state,
-                               adagrad, eps, out_dtype=None, per_id_w=None):
+                               adagrad, eps, out_dtype=None, per_id_w=None,
+                               sr=None):
     return _CsrLookupFusedOptimizer.apply(weight, values, row_splits, combiner,
                                           lr, state, adagrad, eps, out_dtype,
-                                          per_id_w)
+                                          per_id_w, sr)
 
 
 def check_per_id_weights(per_id_w, nnz: int) -> None:

@@ -32,8 +32,8 @@ import torch
 from torch import nn
 
 from ..layers.embedding import Embedding
-from ..ops.embedding_lookup import (Ragged, embedding_lookup,
-                                    quantized_embedding_lookup)
+from ..ops.embedding_lookup import (Ragged, embedding_lookup, mix64_int,
+                                    quantized_embedding_lookup, to_int64)
 from . import comm
 from .strategy import DistEmbeddingStrategy, TableConfig
 
@@ -254,7 +254,9 @@ class DistributedEmbedding(nn.Module):
     def enable_fused_sgd(self, lr: float):
         return self.enable_fused_optimizer("sgd", lr)
 
-    def enable_fused_optimizer(self, method: str, lr: float, eps: float = 1e-10):
+    def enable_fused_optimizer(self, method: str, lr: float, eps: float = 1e-10,
+                               stochastic_rounding: bool = False,
+                               seed: Optional[int] = None):
         """Enables the in-backward fused optimizer (``"sgd"``, ``"adagrad"``
         or ``"rowwise_adagrad"``) on all model-parallel tables (col + row
         groups).  Data-parallel tables keep sparse grads (they need the
@@ -267,11 +269,24 @@ class DistributedEmbedding(nn.Module):
         shard sees only its own columns and takes the row mean over that
         slice, so a column-sliced table does *not* train like the unsliced
         one: each slice has its own per-row step size (TorchRec's column-wise
-        sharding behaves the same way).  The row sums are not all-reduced."""
-        for lyr in list(self.col_layers) + list(self.row_layers):
+        sharding behaves the same way).  The row sums are not all-reduced.
+
+        ``stochastic_rounding`` (bf16 tables, ``table_dtype=torch.bfloat16``)
+        and ``seed`` are the layer's.  Every local layer gets a seed of its
+        own, ``mix64(mix64(mix64(seed) ^ rank) ^ local layer index)``, so no
+        two shards share a bit stream; ``seed=None`` draws the base seed
+        from torch's default CPU generator."""
+        if stochastic_rounding and seed is None:
+            seed = int(torch.randint(0, 1 << 62, (1,)))
+        for i, lyr in enumerate(list(self.col_layers) + list(self.row_layers)):
             if getattr(lyr, "_cpu_offload", False):
                 continue
-            lyr.enable_fused_optimizer(method, lr, eps)
+            lyr_seed = None
+            if stochastic_rounding:
+                lyr_seed = to_int64(mix64_int(
+                    mix64_int(mix64_int(int(seed)) ^ self.rank) ^ i))
+            lyr.enable_fused_optimizer(method, lr, eps, stochastic_rounding,
+                                       lyr_seed)
         return self
 
     def quantize_(self, chunk_rows: int = 1 << 20):

@@ -1,17 +1,21 @@
 #!/usr/bin/env python3
 """Times the in-backward fused update (csr_fused_optimizer_apply) per method.
 
-Shape: the DLRM-bs64k-shaped update of tools/pmc_bw.py (10M x 128 fp32 table,
-1.7M hotness-1 ids, bf16 grads), with uniform and with power-law ids (hot
-rows take the long-segment path).  Methods alternate inside every round so
-that drift hits them alike; each figure is the median over rounds of the mean
-call time, taken with device events.  One JSON line per (ids, method).
+Shape: the DLRM-bs64k-shaped update of tools/pmc_bw.py (10M x 128 table, fp32
+or with --table-dtype bf16, 1.7M hotness-1 ids, bf16 grads), with uniform and
+with power-law ids (hot rows take the long-segment path).  Methods alternate
+inside every round so that drift hits them alike; each figure is the median
+over rounds of the mean call time, taken with device events.  One JSON line
+per (ids, method, rounding).
 
   python tools/bench_fused_update.py [--methods sgd adagrad rowwise_adagrad]
   python tools/bench_fused_update.py --ext OTHER/_hip_ops*.so --methods sgd adagrad
+  python tools/bench_fused_update.py --table-dtype bf16 --stochastic-rounding
 
 --ext times another build of the extension (e.g. the parent commit's) on the
-same inputs.
+same inputs.  --stochastic-rounding (bf16 tables) times every method twice,
+with nearest-even and with stochastic rounding, the two alternating inside
+every round like the methods.
 """
 import argparse
 import importlib.util
@@ -52,13 +56,20 @@ def main():
                    choices=METHODS)
     p.add_argument("--rounds", type=int, default=7)
     p.add_argument("--iters", type=int, default=20)
+    p.add_argument("--table-dtype", choices=("fp32", "bf16"), default="fp32")
+    p.add_argument("--stochastic-rounding", action="store_true",
+                   help="also time stochastic rounding (needs bf16 tables)")
     args = p.parse_args()
     assert torch.cuda.is_available(), "needs a GPU: no timing without one"
+    if args.stochastic_rounding and args.table_dtype != "bf16":
+        p.error("--stochastic-rounding needs --table-dtype bf16")
     ext = load_ext(args.ext)
     from distributed_embeddings_amd.utils.input_gen import power_law_ids
 
     torch.manual_seed(0)
     w = torch.randn(VOCAB, WIDTH, device="cuda")
+    if args.table_dtype == "bf16":
+        w = w.bfloat16()
     splits = torch.arange(NNZ + 1, device="cuda")
     grad = torch.randn(NNZ, WIDTH, device="cuda").bfloat16()
     lr = torch.tensor([1e-3], device="cuda")
@@ -67,35 +78,42 @@ def main():
         "power_law": power_law_ids(VOCAB, (NNZ,), 1.05).cuda(),
     }
     states = {m: state_for(m) for m in args.methods}
+    sr = torch.tensor([1234, 0], device="cuda")  # {seed, step}
+    roundings = ("rne", "sr") if args.stochastic_rounding else ("rne",)
+    variants = [(m, r) for m in args.methods for r in roundings]
 
-    def call(method, ids):
+    def call(variant, ids):
+        method, rounding = variant
+        # the nearest-even call is the parent commit's, argument for argument
+        extra = (None, sr) if rounding == "sr" else ()
         ext.csr_fused_optimizer_apply(w, states[method], ids, splits, grad, lr,
-                                      False, method != "sgd", 1e-10)
+                                      False, method != "sgd", 1e-10, *extra)
 
     for name, ids in id_sets.items():
-        for m in args.methods:
+        for v in variants:
             for _ in range(3):
-                call(m, ids)
+                call(v, ids)
         torch.cuda.synchronize()
-        times = {m: [] for m in args.methods}
+        times = {v: [] for v in variants}
         for _ in range(args.rounds):
-            for m in args.methods:
+            for v in variants:
                 t0 = torch.cuda.Event(enable_timing=True)
                 t1 = torch.cuda.Event(enable_timing=True)
                 t0.record()
                 for _ in range(args.iters):
-                    call(m, ids)
+                    call(v, ids)
                 t1.record()
                 t1.synchronize()
-                times[m].append(t0.elapsed_time(t1) / args.iters * 1e3)
-        for m in args.methods:
+                times[v].append(t0.elapsed_time(t1) / args.iters * 1e3)
+        for v in variants:
             print(json.dumps({
-                "ext": args.ext or "in-tree", "ids": name, "method": m,
+                "ext": args.ext or "in-tree", "ids": name, "method": v[0],
+                "table_dtype": args.table_dtype, "rounding": v[1],
                 "unique_ids": int(torch.unique(ids).numel()),
-                "us_median": round(statistics.median(times[m]), 1),
-                "us_min": round(min(times[m]), 1),
-                "us_max": round(max(times[m]), 1),
-                "state_bytes": states[m].numel() * 4,
+                "us_median": round(statistics.median(times[v]), 1),
+                "us_min": round(min(times[v]), 1),
+                "us_max": round(max(times[v]), 1),
+                "state_bytes": states[v[0]].numel() * 4,
             }), flush=True)
 
 
