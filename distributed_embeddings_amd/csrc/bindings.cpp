@@ -595,10 +595,31 @@ static int64_t* sr_ptr(const std::optional<torch::Tensor>& sr,
   return t.data_ptr<int64_t>();
 }
 
+// Lazy Adam's moments: fp32 [2, vocab, width], m first, on the weight's
+// device; both betas in [0, 1).
+static void check_adam_state(const torch::Tensor& state,
+                             const torch::Tensor& weight, double beta1,
+                             double beta2) {
+  CHECK_CUDA(state); CHECK_CONTIG(state);
+  TORCH_CHECK(state.dtype() == torch::kFloat32, "adam state must be fp32");
+  TORCH_CHECK(state.dim() == 3 && state.size(0) == 2 &&
+              state.size(1) == weight.size(0) &&
+              state.size(2) == weight.size(1),
+              "adam state shape mismatch: expected [2, vocab, width], got ",
+              state.sizes(), " for weight ", weight.sizes());
+  TORCH_CHECK(state.device() == weight.device(),
+              "adam state must be on the weight's device");
+  TORCH_CHECK(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0,
+              "adam betas must lie in [0, 1), got (", beta1, ", ", beta2, ")");
+}
+
+// adam_step > 0 selects lazy Adam at step t = adam_step (the host counts on
+// this path): state is [2, vocab, width] and adagrad has to be false.
 void sparse_row_update(torch::Tensor weight, torch::Tensor state,
                        torch::Tensor ids, torch::Tensor grad, double lr,
                        double eps, bool adagrad,
-                       std::optional<torch::Tensor> sr) {
+                       std::optional<torch::Tensor> sr, int64_t adam_step,
+                       double beta1, double beta2) {
   CHECK_CUDA(weight); CHECK_CUDA(ids); CHECK_CUDA(grad);
   CHECK_CONTIG(weight); CHECK_CONTIG(ids); CHECK_CONTIG(grad);
   TORCH_CHECK(weight.dtype() == torch::kFloat32 ||
@@ -606,6 +627,10 @@ void sparse_row_update(torch::Tensor weight, torch::Tensor state,
   TORCH_CHECK(grad.dtype() == torch::kFloat32);
   TORCH_CHECK(ids.dtype() == torch::kInt64);
   int64_t* sr_p = sr_ptr(sr, weight);
+  TORCH_CHECK(adam_step >= 0, "adam_step must not be negative");
+  const bool adam = adam_step > 0;
+  TORCH_CHECK(!(adam && adagrad), "adam_step and adagrad exclude each other");
+  if (adam) check_adam_state(state, weight, beta1, beta2);
   const int64_t n = ids.numel();
   if (n == 0) return;
   float* state_ptr = nullptr;
@@ -614,11 +639,18 @@ void sparse_row_update(torch::Tensor weight, torch::Tensor state,
     rowwise = check_adagrad_state(state, weight);
     state_ptr = state.data_ptr<float>();
   }
+  AdamConfig cfg{beta1, beta2, weight.size(0), nullptr, nullptr};
+  if (adam) {
+    state_ptr = state.data_ptr<float>();
+    const double t = (double)adam_step;
+    lr = lr * std::sqrt(1.0 - std::pow(beta2, t)) / (1.0 - std::pow(beta1, t));
+  }
   launch_sparse_row_update(weight.data_ptr(),
                            weight.dtype() == torch::kBFloat16, state_ptr,
                            ids.data_ptr<int64_t>(), grad.data_ptr<float>(), n,
                            (int)weight.size(1), (float)lr, (float)eps, adagrad,
-                           rowwise, sr_p, current_stream());
+                           rowwise, sr_p, adam ? &cfg : nullptr,
+                           current_stream());
 }
 
 void csr_fused_optimizer_apply(torch::Tensor weight, torch::Tensor state,
@@ -626,7 +658,12 @@ void csr_fused_optimizer_apply(torch::Tensor weight, torch::Tensor state,
                                torch::Tensor grad_out, torch::Tensor lr,
                                bool mean, bool adagrad, double eps,
                                std::optional<torch::Tensor> per_id_w,
-                               std::optional<torch::Tensor> sr) {
+                               std::optional<torch::Tensor> sr,
+                               std::optional<torch::Tensor> adam_step,
+                               double beta1, double beta2) {
+  // adam_step (int64 [1] on the device) selects lazy Adam: state is
+  // [2, vocab, width], adagrad has to be false, and an apply that launches
+  // adds 1 to the step on the device.
   // All-device sorted pipeline (no host sync; hipGraph-capturable):
   // sort (id, pos) -> permute row-ids -> head-flag unique -> segment pad ->
   // one direct update per unique row (long segments chunked with one atomic
@@ -648,6 +685,17 @@ void csr_fused_optimizer_apply(torch::Tensor weight, torch::Tensor state,
   const int64_t nnz = values.numel();
   const int64_t vocab = weight.size(0);
   const int width = (int)weight.size(1);
+  const bool adam = adam_step.has_value();
+  if (adam) {
+    TORCH_CHECK(!adagrad, "adam_step and adagrad exclude each other");
+    check_adam_state(state, weight, beta1, beta2);
+    const torch::Tensor& t = *adam_step;
+    CHECK_CUDA(t); CHECK_CONTIG(t);
+    TORCH_CHECK(t.dtype() == torch::kInt64 && t.dim() == 1 && t.numel() == 1,
+                "adam_step must be an int64 [1] tensor");
+    TORCH_CHECK(t.device() == weight.device(),
+                "adam_step must be on the weight's device");
+  }
   if (num_rows <= 0 || nnz <= 0) return;
   auto stream = current_stream();
   auto i64 = values.options();
@@ -672,7 +720,15 @@ void csr_fused_optimizer_apply(torch::Tensor weight, torch::Tensor state,
     rowwise = check_adagrad_state(state, weight);
     state_ptr = state.data_ptr<float>();
   }
-  if (adagrad || wbf16) {
+  AdamConfig cfg{beta1, beta2, vocab, nullptr, nullptr};
+  torch::Tensor a_t;
+  if (adam) {
+    state_ptr = state.data_ptr<float>();
+    a_t = torch::empty({1}, f32);
+    cfg.step = adam_step->data_ptr<int64_t>();
+    cfg.a_t = a_t.data_ptr<float>();
+  }
+  if (adagrad || adam || wbf16) {
     scratch_rows = nnz / (128 + 1) + 1;  // max possible long segments
     scratch = torch::empty({scratch_rows, (int64_t)width}, f32);
     scratch_ptr = scratch.data_ptr<float>();
@@ -689,7 +745,8 @@ void csr_fused_optimizer_apply(torch::Tensor weight, torch::Tensor state,
                                  long_count.data_ptr<int32_t>(),
                                  work_items.data_ptr<int64_t>(),
                                  n_work.data_ptr<int32_t>(), scratch_ptr,
-                                 scratch_rows, adagrad, rowwise, sr_p, stream);
+                                 scratch_rows, adagrad, rowwise, sr_p,
+                                 adam ? &cfg : nullptr, stream);
 }
 
 // fp32 [n] -> bf16 [n], stochastically rounded with the bits the fused
@@ -879,18 +936,24 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("integer_lookup", &integer_lookup,
         "open-addressing hash vocab build + lookup (gfx950)");
   m.def("sparse_row_update", &sparse_row_update,
-        "fused sparse SGD/Adagrad/row-wise Adagrad row update (gfx950)",
+        "fused sparse SGD/Adagrad/row-wise Adagrad/lazy Adam row update "
+        "(gfx950)",
         pybind11::arg("weight"), pybind11::arg("state"), pybind11::arg("ids"),
         pybind11::arg("grad"), pybind11::arg("lr"), pybind11::arg("eps"),
-        pybind11::arg("adagrad"), pybind11::arg("sr") = pybind11::none());
+        pybind11::arg("adagrad"), pybind11::arg("sr") = pybind11::none(),
+        pybind11::arg("adam_step") = 0, pybind11::arg("beta1") = 0.9,
+        pybind11::arg("beta2") = 0.999);
   m.def("csr_fused_optimizer_apply", &csr_fused_optimizer_apply,
-        "in-backward fused SGD/Adagrad/row-wise Adagrad update (gfx950)",
+        "in-backward fused SGD/Adagrad/row-wise Adagrad/lazy Adam update "
+        "(gfx950)",
         pybind11::arg("weight"), pybind11::arg("state"),
         pybind11::arg("values"), pybind11::arg("row_splits"),
         pybind11::arg("grad_out"), pybind11::arg("lr"), pybind11::arg("mean"),
         pybind11::arg("adagrad"), pybind11::arg("eps"),
         pybind11::arg("per_id_w") = pybind11::none(),
-        pybind11::arg("sr") = pybind11::none());
+        pybind11::arg("sr") = pybind11::none(),
+        pybind11::arg("adam_step") = pybind11::none(),
+        pybind11::arg("beta1") = 0.9, pybind11::arg("beta2") = 0.999);
   m.def("stochastic_round_bf16", &stochastic_round_bf16,
         "fp32 -> bf16 with the fused optimizers' stochastic rounding (gfx950)",
         pybind11::arg("x"), pybind11::arg("seed"), pybind11::arg("step") = 0,

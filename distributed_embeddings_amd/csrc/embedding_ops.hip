@@ -447,13 +447,49 @@ __device__ __forceinline__ float narrow_reduce(
   return acc;
 }
 
+// Update rule of the element-wise kernels, a template parameter.
+enum : int { RULE_SGD = 0, RULE_ADAGRAD = 1, RULE_ADAM = 2 };
+
+// Lazy Adam's constants.  Its state is m [vocab, width] followed by v
+// [vocab, width]: the kernels get m's base and v_off = vocab * width.
+// omb = 1 - b, rounded once from double on the host.  The other rules carry
+// the struct unread.
+struct AdamArgs {
+  float b1, b2, omb1, omb2;
+  int64_t v_off;
+};
+
 // SGD: w -= lr * g.   Adagrad: s += g^2; w -= lr * g / (sqrt(s) + eps).
-// The new value of a weight w (fp32) and, for Adagrad, the state update.
-template <bool ADAGRAD>
+// Lazy Adam: m = b1 m + (1 - b1) g; v = b2 v + (1 - b2) g^2;
+//            w -= a_t * m / (sqrt(v) + eps), where the caller passes
+//            a_t = lr * sqrt(1 - b2^t) / (1 - b1^t) as lr (adam_advance_step).
+
+// Lazy Adam on registers: updates m and v and returns the new weight.  Both
+// sums are fmas by name in either rounding mode, for the reason given in
+// row_update_value: m and v are the nearest-even run's bit for bit.
+__device__ __forceinline__ float adam_value(float w, float& m, float& v,
+                                            float g, float a_t, float eps,
+                                            const AdamArgs& ad) {
+  m = __builtin_fmaf(ad.b1, m, ad.omb1 * g);
+  v = __builtin_fmaf(ad.b2, v, ad.omb2 * (g * g));
+  return w - a_t * m / (sqrtf(v) + eps);
+}
+
+// The new value of a weight w (fp32) and, for Adagrad and Adam, the state
+// update; state points at the element's s, or at its m.
+template <int RULE>
 __device__ __forceinline__ float row_update_value(float w, float* state,
                                                   float g, float lr, float eps,
-                                                  bool rounding) {
-  if (ADAGRAD) {
+                                                  bool rounding,
+                                                  const AdamArgs& ad) {
+  if constexpr (RULE == RULE_ADAM) {
+    float m = state[0], v = state[ad.v_off];
+    w = adam_value(w, m, v, g, lr, eps, ad);
+    state[0] = m;
+    state[ad.v_off] = v;
+    return w;
+  }
+  if (RULE == RULE_ADAGRAD) {
     // The nearest-even kernels contract this sum to one fma.  The rounding
     // kernels ask for it by name: their wide VEC = 2 instantiation otherwise
     // came out as a packed multiply and a packed add, and the state differed
@@ -468,13 +504,14 @@ __device__ __forceinline__ float row_update_value(float w, float* state,
 
 // w is element o of the table and h = sr_group_hash(sr, o): they pick the
 // stochastic-rounding bits of a bf16 store.
-template <bool ADAGRAD, typename PT>
+template <int RULE, typename PT>
 __device__ __forceinline__ void apply_row_update(PT* w, float* state, float g,
                                                  float lr, float eps,
                                                  SrState sr, uint64_t h,
-                                                 int64_t o) {
+                                                 int64_t o,
+                                                 const AdamArgs& ad) {
   pt_store_sr(w,
-              row_update_value<ADAGRAD>(pt_load(w), state, g, lr, eps, sr.on),
+              row_update_value<RULE>(pt_load(w), state, g, lr, eps, sr.on, ad),
               sr, h, o);
 }
 
@@ -754,6 +791,16 @@ template <typename F>
 static void dispatch_bool(bool b, F&& f) {
   if (b) f(std::true_type{});
   else f(std::false_type{});
+}
+
+// Calls f(Int<RULE>).
+template <typename F>
+static void dispatch_rule(int rule, F&& f) {
+  switch (rule) {
+    case RULE_ADAM: f(Int<RULE_ADAM>{}); break;
+    case RULE_ADAGRAD: f(Int<RULE_ADAGRAD>{}); break;
+    default: f(Int<RULE_SGD>{}); break;
+  }
 }
 
 // Calls f(std::true_type) for a bf16 table with a {seed, step} pair and
@@ -1332,7 +1379,7 @@ void launch_pad_seg_offsets(int64_t* seg, int64_t n, const int32_t* num_unique,
 // direct (non-atomic) update.  Grid-strides only over the REAL segment count
 // (*nu_ptr), not the padded nnz-sized buffer.  srow comes from our own
 // expansion, so the gathers need no bounds check.
-template <int TILE, int VEC, bool HAS_W, bool ADAGRAD, bool SR, typename PT,
+template <int TILE, int VEC, bool HAS_W, int RULE, bool SR, typename PT,
           typename GT>
 __global__ void sorted_opt_update(PT* __restrict__ weight,
                                   float* __restrict__ state, float eps,
@@ -1347,7 +1394,8 @@ __global__ void sorted_opt_update(PT* __restrict__ weight,
                                   int64_t* __restrict__ long_rows,
                                   int32_t* __restrict__ long_count,
                                   int tile_w,
-                                  const int64_t* __restrict__ sr_ptr) {
+                                  const int64_t* __restrict__ sr_ptr,
+                                  AdamArgs ad) {
   const WaveCoord wc = wave_coord();
   const TileCoord tc = tile_coord(wc.lane, TILE > 0 ? WAVE : tile_w);
   const float lr = *lr_ptr;
@@ -1369,8 +1417,9 @@ __global__ void sorted_opt_update(PT* __restrict__ weight,
           grad_out, srow, sw, 0, width, s, e, wc.lane);
       if (wc.lane < TILE && wc.lane < width) {
         const int64_t o = row0 + wc.lane;
-        apply_row_update<ADAGRAD>(&weight[o], ADAGRAD ? &state[o] : nullptr, g,
-                                  lr, eps, sr, sr_group_hash(sr, o), o);
+        apply_row_update<RULE>(&weight[o],
+                               RULE != RULE_SGD ? &state[o] : nullptr, g, lr,
+                               eps, sr, sr_group_hash(sr, o), o, ad);
       }
     } else {
       for (int col0 = tc.tl * VEC; col0 < width; col0 += tile_w * VEC) {
@@ -1380,7 +1429,25 @@ __global__ void sorted_opt_update(PT* __restrict__ weight,
         // VEC divides width and col0, so o0 is a multiple of VEC and its
         // VEC elements sit in one group of four: one hash for all
         const int64_t o0 = row0 + col0;
-        if constexpr (SR) {
+        if constexpr (RULE == RULE_ADAM) {
+          // Each group goes whole into registers and whole back, with one
+          // vector access per array; v_off is a multiple of VEC because
+          // width is.  Left to per-element accesses the apply took 1696 us
+          // on uniform ids (10M x 128 fp32, Adagrad 924 us), this way
+          // 1100 us: m and v share one array a runtime distance apart, so
+          // the compiler may not move a load of one across a store to the
+          // other.
+          float wv[VEC], mv[VEC], vv[VEC];
+          pt_loadv<VEC>(weight + o0, wv);
+          pt_loadv<VEC>(state + o0, mv);
+          pt_loadv<VEC>(state + o0 + ad.v_off, vv);
+#pragma unroll
+          for (int v = 0; v < VEC; ++v)
+            wv[v] = adam_value(wv[v], mv[v], vv[v], acc[v], lr, eps, ad);
+          pt_storev<VEC>(state + o0, mv);
+          pt_storev<VEC>(state + o0 + ad.v_off, vv);
+          pt_storev_sr<VEC>(weight + o0, wv, sr, o0);
+        } else if constexpr (SR) {
           // One vector load and store per group.  The compiler makes these
           // of the nearest-even path's per-element ones, but not once each
           // store branches on finite / non-finite (measured: +24% on SGD,
@@ -1389,17 +1456,17 @@ __global__ void sorted_opt_update(PT* __restrict__ weight,
           pt_loadv<VEC>(weight + o0, wv);
 #pragma unroll
           for (int v = 0; v < VEC; ++v)
-            wv[v] = row_update_value<ADAGRAD>(
-                wv[v], ADAGRAD ? &state[o0 + v] : nullptr, acc[v], lr, eps,
-                true);
+            wv[v] = row_update_value<RULE>(
+                wv[v], RULE != RULE_SGD ? &state[o0 + v] : nullptr, acc[v], lr,
+                eps, true, ad);
           pt_storev_sr<VEC>(weight + o0, wv, sr, o0);
         } else {
 #pragma unroll
           for (int v = 0; v < VEC; ++v) {
             const int64_t o = o0 + v;
-            apply_row_update<ADAGRAD>(&weight[o],
-                                      ADAGRAD ? &state[o] : nullptr, acc[v],
-                                      lr, eps, sr, 0, o);
+            apply_row_update<RULE>(&weight[o],
+                                   RULE != RULE_SGD ? &state[o] : nullptr,
+                                   acc[v], lr, eps, sr, 0, o, ad);
           }
         }
       }
@@ -1539,14 +1606,14 @@ __global__ void sorted_opt_long(float* __restrict__ target,  // weight or scratc
   }
 }
 
-template <bool ADAGRAD, bool SR, typename PT>
+template <int RULE, bool SR, typename PT>
 __global__ void sorted_long_finalize(
     PT* __restrict__ weight, float* __restrict__ state, float eps,
     const int64_t* __restrict__ sorted_ids, const int64_t* __restrict__ seg,
     const float* __restrict__ lr_ptr, int width,
     const int64_t* __restrict__ long_rows,
     const int32_t* __restrict__ long_count, const float* __restrict__ scratch,
-    const int64_t* __restrict__ sr_ptr) {
+    const int64_t* __restrict__ sr_ptr, AdamArgs ad) {
   const WaveCoord wc = wave_coord();
   const float lr = *lr_ptr;
   const int64_t n_long = *long_count;
@@ -1555,9 +1622,10 @@ __global__ void sorted_long_finalize(
     const int64_t uid = sorted_ids[seg[long_rows[li]]];
     for (int c = wc.lane; c < width; c += WAVE) {
       const int64_t o = uid * (int64_t)width + c;
-      apply_row_update<ADAGRAD>(&weight[o], ADAGRAD ? &state[o] : nullptr,
-                                scratch[li * (int64_t)width + c], lr, eps, sr,
-                                sr_group_hash(sr, o), o);
+      apply_row_update<RULE>(&weight[o],
+                             RULE != RULE_SGD ? &state[o] : nullptr,
+                             scratch[li * (int64_t)width + c], lr, eps, sr,
+                             sr_group_hash(sr, o), o, ad);
     }
   }
 }
@@ -1589,18 +1657,40 @@ __global__ void sr_advance_step(int64_t* __restrict__ sr) {
   if (blockIdx.x == 0 && threadIdx.x == 0) sr[1] = sr[1] + 1;
 }
 
+// Begins a lazy-Adam apply: t = ++step[0] and a_t[0] = lr * sqrt(1 - b2^t) /
+// (1 - b1^t), the powers in double.  Every update kernel after it on the
+// stream reads a_t where the other rules read lr, so all of one apply see the
+// same t, and the next apply (or graph replay) the next one.
+__global__ void adam_advance_step(int64_t* __restrict__ step,
+                                  const float* __restrict__ lr_ptr,
+                                  float* __restrict__ a_t, double b1,
+                                  double b2) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  const int64_t t = step[0] + 1;
+  step[0] = t;
+  a_t[0] = (float)((double)*lr_ptr * sqrt(1.0 - pow(b2, (double)t)) /
+                   (1.0 - pow(b1, (double)t)));
+}
+
+static AdamArgs adam_args(const AdamConfig* adam, int width) {
+  if (!adam) return {0.f, 0.f, 0.f, 0.f, 0};
+  return {(float)adam->b1, (float)adam->b2, (float)(1.0 - adam->b1),
+          (float)(1.0 - adam->b2), adam->vocab * (int64_t)width};
+}
+
 template <bool SR, typename PT, typename GT>
 static void launch_sorted_optimizer_update_t(
     PT* weight, float* state, float eps, const int64_t* sorted_ids,
     const int64_t* seg, const int64_t* srow, const float* sw,
     const GT* grad_out, const float* lr, const int32_t* nu_ptr,
     int64_t max_segs, int width, int64_t* long_rows, int32_t* long_count,
-    int64_t* work_items, int32_t* n_work, float* long_scratch, bool adagrad,
-    bool rowwise, const int64_t* sr, hipStream_t stream) {
+    int64_t* work_items, int32_t* n_work, float* long_scratch, int rule,
+    bool rowwise, const int64_t* sr, AdamArgs ad, hipStream_t stream) {
   const dim3 block(256);
   // bf16 weights have no atomicAdd: their long-SGD path also goes through the
   // fp32 scratch + finalize pair.
-  const bool use_scratch = adagrad || !std::is_same<PT, float>::value;
+  const bool use_scratch =
+      rule != RULE_SGD || !std::is_same<PT, float>::value;
   dispatch_width(width, [&](auto tile, auto vec) {
     constexpr int TILE = decltype(tile)::value, VEC = decltype(vec)::value;
     const RowTiling t = row_tiling<TILE, VEC>(width, max_segs);
@@ -1614,13 +1704,13 @@ static void launch_sorted_optimizer_update_t(
             grad_out, lr, nu_ptr, (int64_t)LONG_T, width, long_rows,
             long_count, t.tile_w, sr);
       } else {
-        dispatch_bool(adagrad, [&](auto ada) {
+        dispatch_rule(rule, [&](auto rule_t) {
           hipLaunchKernelGGL(
-              (sorted_opt_update<TILE, VEC, HAS_W, decltype(ada)::value, SR,
+              (sorted_opt_update<TILE, VEC, HAS_W, decltype(rule_t)::value, SR,
                                  PT, GT>),
               grid, block, 0, stream, weight, state, eps, sorted_ids, seg,
               srow, sw, grad_out, lr, nu_ptr, (int64_t)LONG_T, width,
-              long_rows, long_count, t.tile_w, sr);
+              long_rows, long_count, t.tile_w, sr, ad);
         });
       }
       hipLaunchKernelGGL(expand_long_work, dim3(512), block, 0, stream,
@@ -1639,11 +1729,11 @@ static void launch_sorted_optimizer_update_t(
                          block, 0, stream, weight, state, eps, sorted_ids, seg,
                          lr, width, long_rows, long_count, long_scratch, sr);
     else if (use_scratch)
-      dispatch_bool(adagrad, [&](auto ada) {
+      dispatch_rule(rule, [&](auto rule_t) {
         hipLaunchKernelGGL(
-            (sorted_long_finalize<decltype(ada)::value, SR, PT>), dim3(256),
+            (sorted_long_finalize<decltype(rule_t)::value, SR, PT>), dim3(256),
             block, 0, stream, weight, state, eps, sorted_ids, seg, lr, width,
-            long_rows, long_count, long_scratch, sr);
+            long_rows, long_count, long_scratch, sr, ad);
       });
   });
 }
@@ -1660,8 +1750,15 @@ void launch_sorted_optimizer_update(void* weight, bool weight_bf16,
                                     int64_t* work_items, int32_t* n_work,
                                     float* long_scratch, int64_t scratch_rows,
                                     bool adagrad, bool rowwise, int64_t* sr,
+                                    const AdamConfig* adam,
                                     hipStream_t stream) {
   if (!weight_bf16) sr = nullptr;  // fp32 tables do not round
+  const int rule = adam ? RULE_ADAM : adagrad ? RULE_ADAGRAD : RULE_SGD;
+  if (adam) {
+    hipLaunchKernelGGL(adam_advance_step, dim3(1), dim3(WAVE), 0, stream,
+                       adam->step, lr, adam->a_t, adam->b1, adam->b2);
+    lr = adam->a_t;
+  }
   hipMemsetAsync(long_count, 0, sizeof(int32_t), stream);
   hipMemsetAsync(n_work, 0, sizeof(int32_t), stream);
   if (long_scratch) {
@@ -1676,8 +1773,8 @@ void launch_sorted_optimizer_update(void* weight, bool weight_bf16,
         launch_sorted_optimizer_update_t<decltype(sr_t)::value>(
             (PT*)weight, state, eps, sorted_ids, seg, srow, sw,
             (const GT*)grad_out, lr, nu_ptr, max_segs, width, long_rows,
-            long_count, work_items, n_work, long_scratch, adagrad, rowwise,
-            sr, stream);
+            long_count, work_items, n_work, long_scratch, rule,
+            rowwise && !adam, sr, adam_args(adam, width), stream);
       });
     });
   });
@@ -1781,23 +1878,25 @@ void launch_csr_weight_grad(const void* params, bool params_bf16,
 // One wave per row.
 // ---------------------------------------------------------------------------
 
-template <bool ADAGRAD, bool SR, typename PT>
+template <int RULE, bool SR, typename PT>
 __global__ void sparse_row_update(PT* __restrict__ weight,
                                   float* __restrict__ state,
                                   const int64_t* __restrict__ ids,
                                   const float* __restrict__ grad,
                                   int64_t num_rows, int width, float lr,
                                   float eps,
-                                  const int64_t* __restrict__ sr_ptr) {
+                                  const int64_t* __restrict__ sr_ptr,
+                                  AdamArgs ad) {
   const WaveCoord wc = wave_coord();
   const SrState sr = sr_load<SR>(sr_ptr);
   for (int64_t r = wc.wave_id; r < num_rows; r += wc.n_waves) {
     const int64_t row0 = ids[r] * (int64_t)width;
     for (int c = wc.lane; c < width; c += WAVE) {
       const int64_t o = row0 + c;
-      apply_row_update<ADAGRAD>(&weight[o], ADAGRAD ? &state[o] : nullptr,
-                                grad[r * (int64_t)width + c], lr, eps, sr,
-                                sr_group_hash(sr, o), o);
+      apply_row_update<RULE>(&weight[o],
+                             RULE != RULE_SGD ? &state[o] : nullptr,
+                             grad[r * (int64_t)width + c], lr, eps, sr,
+                             sr_group_hash(sr, o), o, ad);
     }
   }
 }
@@ -1825,10 +1924,13 @@ void launch_sparse_row_update(void* weight, bool weight_bf16, float* state,
                               const int64_t* ids, const float* grad,
                               int64_t num_rows, int width, float lr, float eps,
                               bool adagrad, bool rowwise, int64_t* sr,
-                              hipStream_t stream) {
+                              const AdamConfig* adam, hipStream_t stream) {
   const int block = 256;
   const int grid = pick_grid(num_rows, block / WAVE);
   if (!weight_bf16) sr = nullptr;  // fp32 tables do not round
+  const int rule = adam ? RULE_ADAM : adagrad ? RULE_ADAGRAD : RULE_SGD;
+  const AdamArgs ad = adam_args(adam, width);
+  if (adam) rowwise = false;
   dispatch_bool(weight_bf16, [&](auto w_bf16) {
     using PT = storage_t<decltype(w_bf16)>;
     dispatch_sr<PT>(sr, [&](auto sr_t) {
@@ -1839,10 +1941,11 @@ void launch_sparse_row_update(void* weight, bool weight_bf16, float* state,
                            grad, num_rows, width, lr, eps, sr);
         return;
       }
-      dispatch_bool(adagrad, [&](auto ada) {
-        hipLaunchKernelGGL((sparse_row_update<decltype(ada)::value, SR, PT>),
-                           dim3(grid), dim3(block), 0, stream, (PT*)weight,
-                           state, ids, grad, num_rows, width, lr, eps, sr);
+      dispatch_rule(rule, [&](auto rule_t) {
+        hipLaunchKernelGGL(
+            (sparse_row_update<decltype(rule_t)::value, SR, PT>), dim3(grid),
+            dim3(block), 0, stream, (PT*)weight, state, ids, grad, num_rows,
+            width, lr, eps, sr, ad);
       });
     });
   });

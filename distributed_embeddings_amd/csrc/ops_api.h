@@ -92,6 +92,20 @@ void launch_hash_reinsert(const int64_t* old_keys, const int64_t* old_vals,
 void launch_pad_seg_offsets(int64_t* seg, int64_t n, const int32_t* num_unique,
                             const int64_t* valid_end, hipStream_t stream);
 
+// Lazy Adam.  state is then fp32 [2, vocab, width], m first, and adagrad and
+// rowwise are ignored.  launch_sorted_optimizer_update: a leading one-thread
+// kernel sets t = ++step[0] and a_t[0] = lr * sqrt(1 - b2^t) / (1 - b1^t) on
+// the device (step: int64 [1], a_t: one float of scratch) and the update
+// kernels read a_t in place of lr.  launch_sparse_row_update leaves step and
+// a_t alone: its caller passes a_t as lr.
+struct AdamConfig {
+  double b1, b2;
+  int64_t vocab;
+  int64_t* step;
+  float* a_t;
+};
+
+// adam == nullptr selects SGD or Adagrad by the flags.
 // rowwise (row-wise Adagrad) takes state as [vocab] fp32, one float per row,
 // in place of Adagrad's [vocab, width]; it implies adagrad.
 // sr: device pointer to {seed, step}, or nullptr.  With a bf16 weight it
@@ -111,13 +125,14 @@ void launch_sorted_optimizer_update(void* weight, bool weight_bf16,
                                     int64_t* work_items, int32_t* n_work,
                                     float* long_scratch, int64_t scratch_rows,
                                     bool adagrad, bool rowwise, int64_t* sr,
+                                    const AdamConfig* adam,
                                     hipStream_t stream);
 
 void launch_sparse_row_update(void* weight, bool weight_bf16, float* state,
                               const int64_t* ids, const float* grad,
                               int64_t num_rows, int width, float lr, float eps,
                               bool adagrad, bool rowwise, int64_t* sr,
-                              hipStream_t stream);
+                              const AdamConfig* adam, hipStream_t stream);
 
 // out[i] = bf16 of x[i], stochastically rounded with the bits of table offset
 // base_offset + i at (seed, step); out is bf16 [n].

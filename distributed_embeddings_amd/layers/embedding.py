@@ -17,7 +17,7 @@ from torch import nn
 
 from ..ops.embedding_lookup import (Ragged, _csr_lookup_q8,
                                     check_per_id_weights,
-                                    csr_lookup_fused_optimizer,
+                                    check_betas, csr_lookup_fused_optimizer,
                                     dequantize_rowwise_int8, embedding_lookup,
                                     quantize_rowwise_int8,
                                     quantized_embedding_lookup, to_int64)
@@ -190,16 +190,31 @@ class Embedding(nn.Module):
 
     def enable_fused_optimizer(self, method: str, lr: float, eps: float = 1e-10,
                                stochastic_rounding: bool = False,
-                               seed: Optional[int] = None):
+                               seed: Optional[int] = None,
+                               betas=(0.9, 0.999)):
         """In-backward fused optimizer: the lookup's backward applies the
         update directly (no grad tensor, no host sync; the step becomes
         hipGraph-capturable).  The training optimizer must not also update
         this weight (its ``.grad`` stays ``None``).
 
         ``method`` is ``"sgd"``, ``"adagrad"`` (fp32 state
-        ``[input_dim, output_dim]``) or ``"rowwise_adagrad"`` (fp32 state
+        ``[input_dim, output_dim]``), ``"rowwise_adagrad"`` (fp32 state
         ``[input_dim]``: one accumulator per row, fed with the mean square of
-        the row's summed gradient).  Calling it again replaces the state.
+        the row's summed gradient) or ``"lazy_adam"``.  Calling it again
+        replaces the state.
+
+        ``"lazy_adam"`` is ``torch.optim.SparseAdam``'s update with ``betas``
+        (each in ``[0, 1)``, else ``ValueError``): rows whose id occurs in
+        the step get ``m = b1 m + (1 - b1) G``, ``v = b2 v + (1 - b2) G^2``
+        and ``w -= lr sqrt(1 - b2^t) / (1 - b1^t) * m / (sqrt(v) + eps)`` on
+        their summed gradient ``G``; all other rows keep ``w``, ``m`` and
+        ``v`` bit for bit (no decay).  The moments are the fp32 buffer
+        ``_fused_state`` ``[2, input_dim, output_dim]`` (``m`` first)
+        whatever the table dtype: 8 bytes per table element.  ``t`` is the
+        int64 buffer ``_fused_step`` ``[1]``; it counts the applied updates
+        on the device and is part of ``state_dict``, so a resumed run
+        continues at the right ``t``.  ``eps`` keeps its Adagrad default of
+        ``1e-10``; Adam users normally pass ``1e-8``.
 
         ``stochastic_rounding`` (bf16 tables only; ``ValueError`` on fp32)
         stores the updated weights with stochastic instead of nearest-even
@@ -210,8 +225,9 @@ class Embedding(nn.Module):
         ``state_dict``, so a resumed run continues the bit stream.
         ``seed=None`` draws the seed from torch's default CPU generator
         (``torch.manual_seed`` makes runs repeatable)."""
-        if method not in ("sgd", "adagrad", "rowwise_adagrad"):
+        if method not in ("sgd", "adagrad", "rowwise_adagrad", "lazy_adam"):
             raise ValueError(f"unknown fused optimizer {method!r}")
+        check_betas(betas)
         if self.quantized:
             raise RuntimeError("a quantized (int8) table is inference-only: "
                                "it takes no optimizer")
@@ -219,7 +235,7 @@ class Embedding(nn.Module):
             raise ValueError("stochastic_rounding needs a bf16 table: an "
                              f"{self.weight.dtype} table has nothing to round")
         # allow re-configuring
-        for name in ("_fused_lr", "_fused_state", "_fused_sr"):
+        for name in ("_fused_lr", "_fused_state", "_fused_sr", "_fused_step"):
             if name in self._buffers:
                 del self._buffers[name]
         self.register_buffer("_fused_lr",
@@ -227,7 +243,16 @@ class Embedding(nn.Module):
                                           device=self.weight.device))
         self._fused_method = method
         self._fused_eps = float(eps)
-        if method in ("adagrad", "rowwise_adagrad"):
+        self._fused_betas = (float(betas[0]), float(betas[1]))
+        if method == "lazy_adam":
+            self.register_buffer("_fused_state",
+                                 torch.zeros((2,) + tuple(self.weight.shape),
+                                             dtype=torch.float32,
+                                             device=self.weight.device))
+            self.register_buffer("_fused_step",
+                                 torch.zeros(1, dtype=torch.int64,
+                                             device=self.weight.device))
+        elif method in ("adagrad", "rowwise_adagrad"):
             # fp32 state regardless of table storage dtype
             shape = (self.weight.shape if method == "adagrad"
                      else self.weight.shape[:1])
@@ -242,6 +267,8 @@ class Embedding(nn.Module):
         # weight itself carries de_local when model-parallel)
         self._fused_state.de_local = getattr(self.weight, "de_local", False)
         self._fused_lr.de_local = False  # lr is global; broadcasting is fine
+        if method == "lazy_adam":
+            self._fused_step.de_local = self._fused_state.de_local
         if stochastic_rounding:
             if seed is None:
                 seed = int(torch.randint(0, 1 << 62, (1,)))
@@ -279,11 +306,15 @@ class Embedding(nn.Module):
                 return _csr_lookup_q8(self.qweight, values, row_splits,
                                       combiner, out_dtype, per_id_w)
         if getattr(self, "_fused_lr", None) is not None and self.training:
+            adam = None
+            if self._fused_method == "lazy_adam":
+                adam = (self._fused_step,) + self._fused_betas
             return csr_lookup_fused_optimizer(
                 self.weight, values, row_splits, combiner, self._fused_lr,
-                self._fused_state, self._fused_method != "sgd",
+                self._fused_state,
+                self._fused_method in ("adagrad", "rowwise_adagrad"),
                 self._fused_eps, out_dtype, per_id_w,
-                getattr(self, "_fused_sr", None))
+                getattr(self, "_fused_sr", None), adam)
         from ..ops.embedding_lookup import _CsrLookup
         return _CsrLookup.apply(self.weight, values, row_splits, combiner,
                                 out_dtype, per_id_w)

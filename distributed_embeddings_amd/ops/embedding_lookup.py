@@ -383,6 +383,44 @@ def _write_rows_sr(weight, ids, new_rows, sr) -> None:
     sr[1] += 1
 
 
+def check_betas(betas) -> None:
+    """Raises ValueError unless both Adam betas lie in ``[0, 1)``."""
+    if len(betas) != 2 or not all(0.0 <= float(b) < 1.0 for b in betas):
+        raise ValueError(f"betas must be two values in [0, 1), got {betas!r}")
+
+
+def _check_adam(adam, adagrad, state, weight) -> None:
+    if adam is None:
+        return
+    step, beta1, beta2 = adam
+    if adagrad:
+        raise ValueError("adam and adagrad exclude each other")
+    check_betas((beta1, beta2))
+    if (state.dtype != torch.float32 or state.device != weight.device
+            or state.shape != (2,) + tuple(weight.shape)):
+        raise ValueError("lazy Adam needs an fp32 state [2, vocab, width] on "
+                         f"the weight's device, got {tuple(state.shape)} "
+                         f"{state.dtype} for weight {tuple(weight.shape)}")
+    if (step.dtype != torch.int64 or step.shape != (1,)
+            or step.device != weight.device):
+        raise ValueError("the Adam step must be an int64 [1] tensor on the "
+                         "weight's device")
+
+
+def _lazy_adam_rows(state, ids, g, lr, beta1, beta2, eps, t):
+    """Lazy Adam at step ``t`` on the rows ``ids`` (unique) of the fp32 state
+    ``[2, vocab, ...]`` with their fp32 summed gradients ``g``: updates ``m``
+    and ``v`` of those rows in place and returns the rows' weight delta.  The
+    fp32 torch-op form of the update the HIP kernels apply."""
+    m = state[0].index_select(0, ids).mul_(beta1).add_(g, alpha=1.0 - beta1)
+    v = state[1].index_select(0, ids).mul_(beta2).addcmul_(
+        g, g, value=1.0 - beta2)
+    state[0].index_copy_(0, ids, m)
+    state[1].index_copy_(0, ids, v)
+    a_t = lr * (1.0 - beta2 ** t) ** 0.5 / (1.0 - beta1 ** t)
+    return m.mul_(-a_t).div_(v.sqrt_().add_(eps))
+
+
 class _CsrLookupFusedOptimizer(torch.autograd.Function):
     """CSR lookup whose backward applies the optimizer update in place.
 
@@ -404,18 +442,35 @@ class _CsrLookupFusedOptimizer(torch.autograd.Function):
     stochastic rounding (``stochastic_round_bf16`` at the elements' table
     offsets) and every backward that applies an update adds 1 to ``sr[1]`` --
     on the device, so a captured step draws fresh bits on every replay.
+
+    ``adam`` (optional): ``(step, beta1, beta2)`` selects lazy Adam
+    (``adagrad`` then has to be false).  ``state`` is fp32
+    ``[2, vocab, width]``, ``m`` first, and ``step`` an int64 ``[1]`` tensor
+    on the weight's device.  A backward that applies an update first adds 1
+    to ``step`` -- on the device, so every replay of a captured step takes
+    the next ``t`` -- and then, for every unique in-range id ``u`` with
+    summed gradient row ``G[u]``::
+
+        m[u] = b1 m[u] + (1 - b1) G[u]
+        v[u] = b2 v[u] + (1 - b2) G[u]^2
+        w[u] -= lr sqrt(1 - b2^t) / (1 - b1^t) * m[u] / (sqrt(v[u]) + eps)
+
+    in fp32, which is ``torch.optim.SparseAdam``'s update.  Rows whose id
+    does not occur keep ``w``, ``m`` and ``v`` bit for bit.
     """
 
     @staticmethod
     def forward(ctx, weight, values, row_splits, combiner, lr, state, adagrad,
-                eps, out_dtype=None, per_id_w=None, sr=None):
+                eps, out_dtype=None, per_id_w=None, sr=None, adam=None):
         _check_sr(sr, weight)
+        _check_adam(adam, adagrad, state, weight)
         w32 = _kernel_weights(per_id_w)
         need_dw = per_id_w is not None and ctx.needs_input_grad[9]
         ctx.save_for_backward(weight, values, row_splits, lr, state, w32)
-        # an int64 counter the backward itself advances: kept off the saved
+        # int64 counters the backward itself advances: kept off the saved
         # tensors, whose version check would reject that
         ctx.sr = sr
+        ctx.adam = adam
         ctx.combiner = combiner
         ctx.adagrad = adagrad
         ctx.eps = eps
@@ -438,7 +493,15 @@ class _CsrLookupFusedOptimizer(torch.autograd.Function):
                 # before the update: the table as the forward read it
                 dw = _csr_weight_grad(grad_out, weight, values, row_splits,
                                       ctx.combiner).to(ctx.dw_dtype)
-            if weight.is_cuda:
+            adam = ctx.adam
+            # the kernels' condition for launching (and advancing the steps)
+            launches = values.numel() > 0 and row_splits.numel() > 1
+            if weight.is_cuda and adam is not None:
+                _backend.ops().csr_fused_optimizer_apply(
+                    weight, state, values, row_splits, grad_out, lr,
+                    ctx.combiner == "mean", False, ctx.eps, w32, sr,
+                    adam_step=adam[0], beta1=adam[1], beta2=adam[2])
+            elif weight.is_cuda:
                 _backend.ops().csr_fused_optimizer_apply(
                     weight, state, values, row_splits, grad_out, lr,
                     ctx.combiner == "mean", ctx.adagrad, ctx.eps, w32, sr)
@@ -447,7 +510,15 @@ class _CsrLookupFusedOptimizer(torch.autograd.Function):
                     grad_out.float(), values, row_splits, weight.shape[0],
                     ctx.combiner, w32)
                 lr_v = lr.item()
-                if ctx.adagrad:
+                if adam is not None:
+                    delta = None
+                    if launches:
+                        step = adam[0]
+                        step += 1
+                        delta = _lazy_adam_rows(
+                            state, unique_ids, unique_grad, lr_v, adam[1],
+                            adam[2], ctx.eps, int(step))
+                elif ctx.adagrad:
                     sq = unique_grad * unique_grad
                     rowwise = state.dim() == 1
                     state.index_add_(0, unique_ids,
@@ -458,13 +529,14 @@ class _CsrLookupFusedOptimizer(torch.autograd.Function):
                     delta = -lr_v * unique_grad / denom
                 else:
                     delta = unique_grad * (-lr_v)
-                if sr is None:
+                if delta is None:
+                    pass
+                elif sr is None:
                     weight.index_add_(0, unique_ids, delta.to(weight.dtype))
-                elif values.numel() > 0 and row_splits.numel() > 1:
-                    # the kernels' condition for launching (and advancing)
+                elif launches:
                     rows = weight.index_select(0, unique_ids).float() + delta
                     _write_rows_sr(weight, unique_ids, rows, sr)
-        return (None,) * 9 + (dw, None)
+        return (None,) * 9 + (dw, None, None)
 
 
 def csr_lookup_fused_sgd(weight, values, row_splits, combiner, lr,
@@ -477,10 +549,10 @@ def csr_lookup_fused_sgd(weight, values, row_splits, combiner, lr,
 
 def csr_lookup_fused_optimizer(weight, values, row_splits, combiner, lr, state,
                                adagrad, eps, out_dtype=None, per_id_w=None,
-                               sr=None):
+                               sr=None, adam=None):
     return _CsrLookupFusedOptimizer.apply(weight, values, row_splits, combiner,
                                           lr, state, adagrad, eps, out_dtype,
-                                          per_id_w, sr)
+                                          per_id_w, sr, adam)
 
 
 def check_per_id_weights(per_id_w, nnz: int) -> None:

@@ -256,10 +256,11 @@ class DistributedEmbedding(nn.Module):
 
     def enable_fused_optimizer(self, method: str, lr: float, eps: float = 1e-10,
                                stochastic_rounding: bool = False,
-                               seed: Optional[int] = None):
-        """Enables the in-backward fused optimizer (``"sgd"``, ``"adagrad"``
-        or ``"rowwise_adagrad"``) on all model-parallel tables (col + row
-        groups).  Data-parallel tables keep sparse grads (they need the
+                               seed: Optional[int] = None,
+                               betas=(0.9, 0.999)):
+        """Enables the in-backward fused optimizer (``"sgd"``, ``"adagrad"``,
+        ``"rowwise_adagrad"`` or ``"lazy_adam"``, which takes ``betas``) on
+        all model-parallel tables (col + row groups).  Data-parallel tables keep sparse grads (they need the
         allreduce); CPU-offloaded tables keep sparse grads too (their lookup
         runs through the CPU fallback, not the HIP fused kernel).
         See Embedding.enable_fused_optimizer.
@@ -270,6 +271,11 @@ class DistributedEmbedding(nn.Module):
         slice, so a column-sliced table does *not* train like the unsliced
         one: each slice has its own per-row step size (TorchRec's column-wise
         sharding behaves the same way).  The row sums are not all-reduced.
+
+        Lazy Adam is element-wise: every element's ``m``, ``v`` and update
+        depend on that element's summed gradient alone, and every shard
+        counts the same steps.  Row-sliced and column-sliced shards
+        therefore train exactly like the undistributed table.
 
         ``stochastic_rounding`` (bf16 tables, ``table_dtype=torch.bfloat16``)
         and ``seed`` are the layer's.  Every local layer gets a seed of its
@@ -286,7 +292,7 @@ class DistributedEmbedding(nn.Module):
                 lyr_seed = to_int64(mix64_int(
                     mix64_int(mix64_int(int(seed)) ^ self.rank) ^ i))
             lyr.enable_fused_optimizer(method, lr, eps, stochastic_rounding,
-                                       lyr_seed)
+                                       lyr_seed, betas)
         return self
 
     def quantize_(self, chunk_rows: int = 1 << 20):

@@ -37,7 +37,11 @@ def parse_args():
     p.add_argument("--alpha", type=float, default=1.05)
     p.add_argument("--column-slice-threshold", type=int, default=None)
     p.add_argument("--dp-input", action="store_true", default=True)
-    p.add_argument("--optimizer", default="adagrad", choices=["adagrad", "rowwise_adagrad", "sgd"])
+    p.add_argument("--optimizer", default="adagrad",
+                   choices=["adagrad", "rowwise_adagrad", "sgd", "lazy_adam"],
+                   help="lazy_adam is the reference benchmark's adam: "
+                        "SparseAdam's update, 8 B of fp32 moments per table "
+                        "element")
     p.add_argument("--pool", type=int, default=4)
     p.add_argument("--graph", dest="graph", action="store_true", default=True,
                    help="hipGraph-capture the step (world==1; eager fallback)")
@@ -98,9 +102,12 @@ def main():
         return [p.view(s) for p, s in
                 zip(torch.split(flat, cat_sizes), cat_shapes)]
 
+    # Adam's customary eps; the Adagrad methods keep the optimizers' default
+    eps = 1e-8 if args.optimizer == "lazy_adam" else 1e-10
     opt = de.DistributedOptimizer(SparseEmbeddingOptimizer(
-        model.parameters(), lr=0.01, method=args.optimizer), average=False)
-    model.embeddings.enable_fused_optimizer(args.optimizer, 0.01)
+        model.parameters(), lr=0.01, method=args.optimizer, eps=eps),
+        average=False)
+    model.embeddings.enable_fused_optimizer(args.optimizer, 0.01, eps)
     de.broadcast_parameters(model)
     _loss_sum = torch.nn.BCEWithLogitsLoss(reduction="sum")
     loss_fn = lambda lg, lb: _loss_sum(lg, lb) / args.batch_size

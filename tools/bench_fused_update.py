@@ -9,13 +9,16 @@ over rounds of the mean call time, taken with device events.  One JSON line
 per (ids, method, rounding).
 
   python tools/bench_fused_update.py [--methods sgd adagrad rowwise_adagrad]
+  python tools/bench_fused_update.py --methods adagrad lazy_adam
   python tools/bench_fused_update.py --ext OTHER/_hip_ops*.so --methods sgd adagrad
   python tools/bench_fused_update.py --table-dtype bf16 --stochastic-rounding
 
 --ext times another build of the extension (e.g. the parent commit's) on the
 same inputs.  --stochastic-rounding (bf16 tables) times every method twice,
 with nearest-even and with stochastic rounding, the two alternating inside
-every round like the methods.
+every round like the methods.  lazy_adam needs this tree's build: its state
+is the [2, VOCAB, WIDTH] moments (10 GB) and it counts its steps in a device
+tensor.
 """
 import argparse
 import importlib.util
@@ -29,7 +32,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 
 VOCAB, WIDTH, NNZ = 10_000_000, 128, 1_700_000
-METHODS = ("sgd", "adagrad", "rowwise_adagrad")
+METHODS = ("sgd", "adagrad", "rowwise_adagrad", "lazy_adam")
 
 
 def load_ext(path):
@@ -45,6 +48,8 @@ def load_ext(path):
 def state_for(method):
     if method == "sgd":
         return torch.empty(0, device="cuda")
+    if method == "lazy_adam":
+        return torch.zeros(2, VOCAB, WIDTH, device="cuda")
     shape = (VOCAB, WIDTH) if method == "adagrad" else (VOCAB,)
     return torch.zeros(shape, device="cuda")
 
@@ -79,6 +84,7 @@ def main():
     }
     states = {m: state_for(m) for m in args.methods}
     sr = torch.tensor([1234, 0], device="cuda")  # {seed, step}
+    adam_step = torch.zeros(1, dtype=torch.int64, device="cuda")
     roundings = ("rne", "sr") if args.stochastic_rounding else ("rne",)
     variants = [(m, r) for m in args.methods for r in roundings]
 
@@ -86,6 +92,11 @@ def main():
         method, rounding = variant
         # the nearest-even call is the parent commit's, argument for argument
         extra = (None, sr) if rounding == "sr" else ()
+        if method == "lazy_adam":
+            ext.csr_fused_optimizer_apply(w, states[method], ids, splits, grad,
+                                          lr, False, False, 1e-8, *extra,
+                                          adam_step=adam_step)
+            return
         ext.csr_fused_optimizer_apply(w, states[method], ids, splits, grad, lr,
                                       False, method != "sgd", 1e-10, *extra)
 
