@@ -2022,6 +2022,9 @@ __global__ void hash_insert(const int64_t* __restrict__ keys, int64_t n,
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const int64_t key = keys[i];
+  // key == EMPTY is the OOV token: no slot, no value (a CAS of EMPTY over
+  // EMPTY would "claim" a slot that stays empty and still draw a value)
+  if (key == IL_EMPTY) return;
   uint64_t slot = mix64((uint64_t)key) % (uint64_t)capacity;
   for (int64_t probe = 0; probe < capacity; ++probe) {
     int64_t prev = (int64_t)atomicCAS((unsigned long long*)&tkeys[slot],
@@ -2049,7 +2052,9 @@ __global__ void hash_find(const int64_t* __restrict__ keys, int64_t n,
   const int64_t key = keys[i];
   uint64_t slot = mix64((uint64_t)key) % (uint64_t)capacity;
   int64_t value = 0;
-  for (int64_t probe = 0; probe < capacity; ++probe) {
+  // the OOV token (key == EMPTY) is value 0 without probing: it would match
+  // the first empty slot and read that slot's unowned tvals
+  for (int64_t probe = 0; key != IL_EMPTY && probe < capacity; ++probe) {
     const int64_t k = tkeys[slot];
     if (k == key) {
       value = tvals[slot];

@@ -1,7 +1,7 @@
 """IntegerLookup — on-the-fly vocabulary build + lookup for raw int64 keys.
 
 MI355X-native equivalent of the reference layer
-(``/root/reference/distributed_embeddings/python/layers/embedding.py:202-281``).
+(``distributed_embeddings/python/layers/embedding.py:202-281``).
 On GPU the vocabulary lives in a hand-written open-addressing (linear-probe)
 int64 hash resident in module buffers — replacing the reference's
 cuCollections ``static_map`` (``embedding_lookup_kernels.cu:383-516``) with a
@@ -14,6 +14,15 @@ not a Python loop).
 Semantics:
 * value 0 is reserved for OOV / overflow (slot pre-claimed at init,
   parity ``embedding.py:217-220``);
+* key -1 is the OOV token, on CPU and GPU, with and without ``auto_grow``
+  (it is also the empty-slot marker of the table): it maps to 0, is counted
+  in ``counts[0]``, never occupies a slot, never draws a value, is never
+  "unresolved" and never triggers growth.  Every other int64 value —
+  negative ones, ``INT64_MIN`` and ``INT64_MAX`` included — is an ordinary
+  key;
+* ``get_vocabulary()`` is ``[-1]`` + the keys with value > 0 in value order:
+  ``vocab[v]`` is the key of value ``v`` and ``len(vocab) ==
+  vocabulary_size()``; value-0 (overflow-pinned) entries are left out;
 * new keys are assigned the next free value (1, 2, ...) on first sight;
 * when the table is full, unseen keys map to 0 (with ``auto_grow=True`` the
   table instead rehashes into doubled capacity — an MI355X extension beyond
@@ -31,6 +40,7 @@ from ..ops import _backend
 
 _LOAD_FACTOR = 1.5  # capacity multiplier, parity: reference embedding.py:226
 _GROW_AT = 0.8      # auto_grow trigger: assigned values / max_tokens
+_EMPTY = -1         # empty-slot marker (IL_EMPTY in embedding_ops.hip) = OOV key
 
 
 def _mix64_np(k: np.ndarray) -> np.ndarray:
@@ -147,11 +157,17 @@ class IntegerLookup(nn.Module):
         uniq, first_idx, inverse = np.unique(flat, return_index=True,
                                              return_inverse=True)
         vals, found, hit_slot = self._probe_np(uniq)
+        # key -1 is the OOV token: value 0, never a miss, never an upgrade
+        # (the probe "hits" it on the first empty slot it meets)
+        sentinel = uniq == _EMPTY
+        vals[sentinel] = 0
+        found[sentinel] = True
+        hit_slot[sentinel] = -1
         miss = np.flatnonzero(~found)
         # under auto_grow, keys a full GPU table once pinned to value 0 are
         # assignable again (their slot value upgrades in place)
-        upgrade = np.flatnonzero(found & (vals == 0)) if self.auto_grow \
-            else np.empty(0, dtype=np.int64)
+        upgrade = np.flatnonzero(found & (vals == 0) & ~sentinel) \
+            if self.auto_grow else np.empty(0, dtype=np.int64)
         need = np.concatenate([miss, upgrade])
         if need.size:
             # assign values in first-occurrence order (reference CPU parity)
@@ -161,6 +177,9 @@ class IntegerLookup(nn.Module):
                 while next_val + need.size > self.max_tokens + 1 or \
                         next_val + need.size > _GROW_AT * self.max_tokens:
                     self._grow()
+                    # the rehash dropped every value-0 entry: the pinned keys
+                    # are absent from the new table and insert like misses
+                    hit_slot[upgrade] = -1
             n_assign = max(0, min(need.size, self.max_tokens + 1 - next_val))
             take = need[:n_assign]
             new_vals = next_val + np.arange(n_assign, dtype=np.int64)
@@ -246,7 +265,9 @@ class IntegerLookup(nn.Module):
                 # their counts[0] contribution, grow, resolve just that
                 # subset — resolved keys keep their counts, so the counts>0
                 # free-value invariant holds throughout.
-                unresolved = out == 0
+                # Key -1 is the OOV token: its 0 is final.
+                unresolved = (out == 0) & \
+                    (keys.contiguous().reshape(-1) != _EMPTY)
                 n0 = int(unresolved.sum().item())
                 if n0:
                     # counts[0] retraction does NOT change vocabulary_size()
@@ -274,6 +295,10 @@ class IntegerLookup(nn.Module):
             self.max_tokens = cn.numel() - 1
             self.counts = torch.empty_like(cn, device=self.counts.device)
         super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
+        # the loaded table may be full: restart the auto_grow bookkeeping
+        # from the one bound that holds for any table, so that the next
+        # forward takes an exact count
+        self._known_used, self._unseen = self.counts.numel(), 0
 
     # ------------------------------------------------------------- inspection
 
@@ -281,14 +306,16 @@ class IntegerLookup(nn.Module):
         return int((self.counts > 0).sum().item())
 
     def get_vocabulary(self) -> List[int]:
-        """Keys in value order; value 0 (OOV) reported as -1 placeholder.
+        """``[-1]`` + the keys with value > 0 in value order, so that
+        ``vocab[v]`` is the key of value ``v`` and ``len(vocab) ==
+        vocabulary_size()``.  Occupied means ``key != -1`` (negative keys are
+        ordinary keys); value-0 entries (keys a full GPU table pinned to OOV)
+        are left out.
 
         Parity: reference ``get_vocabulary`` (``embedding.py:255-281``).
         """
-        keys = self.table_keys.cpu()
-        vals = self.table_values.cpu()
-        occupied = keys >= 0
-        pairs = sorted(zip(vals[occupied].tolist(), keys[occupied].tolist()))
-        vocab = [-1]
-        vocab.extend(k for _, k in pairs)
-        return vocab
+        keys = self.table_keys.cpu().numpy()
+        vals = self.table_values.cpu().numpy()
+        live = (keys != _EMPTY) & (vals > 0)
+        order = np.argsort(vals[live], kind="stable")
+        return [-1] + keys[live][order].tolist()

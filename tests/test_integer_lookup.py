@@ -34,6 +34,12 @@ def test_get_vocabulary():
     vocab = lk.get_vocabulary()
     assert vocab == [-1, 42, 17, 99]
     assert lk.vocabulary_size() == 4  # incl. OOV slot
+    # negative keys are ordinary keys; -1 is the OOV token and adds nothing
+    out = lk(torch.tensor([-1, -5, 17, -1]))
+    assert out.tolist() == [0, 4, 2, 0]
+    vocab = lk.get_vocabulary()
+    assert vocab == [-1, 42, 17, 99, -5]
+    assert len(vocab) == lk.vocabulary_size() == 5
 
 
 def test_nd_input_shape():
