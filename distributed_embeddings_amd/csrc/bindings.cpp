@@ -885,6 +885,46 @@ std::vector<torch::Tensor> relu_bwd_bias_grad(torch::Tensor grad_out,
   return {grad_in, bias_grad};
 }
 
+// Weight gradient of a Linear layer, gw = bf16(g^T x) with fp32 accumulation
+// (wgrad_splitk.hip).  The slab comes from the torch allocator and both
+// launches go on the current stream: capturable.  splitk > 0 and tile >= 0
+// replace the plan's number of K-slices and tile geometry.
+torch::Tensor wgrad_splitk(torch::Tensor g, torch::Tensor x, int64_t splitk,
+                           int64_t tile) {
+  CHECK_CUDA(g); CHECK_CUDA(x);
+  CHECK_CONTIG(g); CHECK_CONTIG(x);
+  TORCH_CHECK(g.dtype() == torch::kBFloat16 && x.dtype() == torch::kBFloat16,
+              "bf16 required");
+  TORCH_CHECK(g.dim() == 2 && x.dim() == 2 && g.size(0) == x.size(0),
+              "g must be [K, M] and x [K, N]");
+  const int64_t K = g.size(0), M = g.size(1), N = x.size(1);
+  TORCH_CHECK(splitk >= 0, "splitk must not be negative");
+  TORCH_CHECK(tile >= -1 && tile <= 2, "tile must be -1 (plan), 0, 1 or 2");
+  WgradSplitkPlan plan;
+  TORCH_CHECK(wgrad_splitk_plan_with(K, M, N, splitk, (int)tile, &plan),
+              "wgrad_splitk takes K >= 1, M % 8 == 0 and N % 8 == 0 or "
+              "N <= 16 (tile 2 for N <= 16 only); got K=", K, " M=", M,
+              " N=", N, " tile=", tile);
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(g.data_ptr()) % 16 == 0 &&
+              reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0,
+              "operands must be 16-byte aligned");
+  auto gw = torch::empty({M, N}, g.options());
+  auto slab = torch::empty({plan.splitk, M, plan.np},
+                           g.options().dtype(torch::kFloat32));
+  launch_wgrad_splitk(g.data_ptr(), x.data_ptr(), slab.data_ptr<float>(),
+                      gw.data_ptr(), K, (int)M, (int)N, plan,
+                      current_stream());
+  return gw;
+}
+
+// (use, splitk, tile geometry) of the plan; use == false also for shapes the
+// kernels do not take
+std::vector<int64_t> wgrad_splitk_plan_py(int64_t K, int64_t M, int64_t N) {
+  WgradSplitkPlan plan;
+  if (!wgrad_splitk_plan(K, M, N, &plan)) return {0, 0, -1};
+  return {plan.use ? 1 : 0, plan.splitk, plan.cfg};
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -969,4 +1009,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("relu_bwd_bias_grad", &relu_bwd_bias_grad,
         "ReLU backward + bias gradient in one pass -> (grad_in, bias_grad) "
         "(gfx950)");
+  m.def("wgrad_splitk", &wgrad_splitk,
+        "Linear weight gradient bf16(g^T x), split-K (MFMA bf16, gfx950)",
+        pybind11::arg("g"), pybind11::arg("x"), pybind11::arg("splitk") = 0,
+        pybind11::arg("tile") = -1);
+  m.def("wgrad_splitk_plan", &wgrad_splitk_plan_py,
+        "(use, splitk, tile geometry) for g [K, M], x [K, N]");
 }

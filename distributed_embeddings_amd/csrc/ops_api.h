@@ -167,6 +167,26 @@ void launch_relu_bwd_bias_grad(const void* grad_out, const void* y,
                                int64_t B, int N, int64_t rows_per_chunk,
                                int64_t num_chunks, hipStream_t stream);
 
+// wgrad_splitk.hip.  gw [M, N] = bf16(g^T x) for bf16 g [K, M], x [K, N], fp32
+// accumulation, one rounding: split-K partial products into the fp32 slab
+// [splitk, M, np], then a fixed-order sum.  M % 8 == 0; N % 8 == 0 or N <= 16.
+struct WgradSplitkPlan {
+  int cfg;         // tile geometry
+  int splitk;      // K-slices, none empty
+  int64_t kslice;  // rows of g and x per slice
+  int np;          // slab row length: N rounded up to 4
+  bool use;        // route the MLP's weight gradient of this shape here
+};
+// false: the kernels do not take this shape
+bool wgrad_splitk_plan(int64_t K, int64_t M, int64_t N, WgradSplitkPlan* plan);
+// splitk >= 1 (capped at ceil(K / 64)) and tile >= 0 replace the plan's
+// choices (tests, tuning)
+bool wgrad_splitk_plan_with(int64_t K, int64_t M, int64_t N, int64_t splitk,
+                            int tile, WgradSplitkPlan* plan);
+void launch_wgrad_splitk(const void* g, const void* x, float* slab, void* gw,
+                         int64_t K, int M, int N, const WgradSplitkPlan& plan,
+                         hipStream_t stream);
+
 size_t custom_radix_sort_hist_elems(int64_t n);
 int custom_radix_sort_num_variants();
 // keys per block of tile geometry `variant` in [0, num_variants)

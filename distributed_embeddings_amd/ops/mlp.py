@@ -7,7 +7,12 @@ re-reads what the first wrote.  ``MLP`` keeps the module tree, the parameter
 names and every GEMM call of that path and replaces the two passes by one
 (``relu_bwd_bias_grad``, ``csrc/mlp_ops.hip``).
 
-``DE_FUSED_MLP=0`` switches the fast path off (plain ``nn.Sequential``).
+The weight gradient ``g.t().mm(x)``, summed over the batch, goes to the
+split-K kernels of ``csrc/wgrad_splitk.hip`` at the shapes their plan routes
+(``weight_grad``).
+
+``DE_FUSED_MLP=0`` switches the fast path off (plain ``nn.Sequential``);
+``DE_WGRAD_SPLITK=0`` keeps the weight gradients on the GEMM library.
 """
 
 import os
@@ -36,13 +41,35 @@ def relu_bwd_bias_grad(grad_out: torch.Tensor,
     return g, g.sum(0)
 
 
+def _wgrad_routed(k: int, m: int, n: int) -> bool:
+    """Whether the plan (``wgrad_splitk_plan``) sends this shape to the kernel."""
+    return bool(_backend.ops().wgrad_splitk_plan(k, m, n)[0])
+
+
+def weight_grad(g: torch.Tensor, xb: torch.Tensor) -> torch.Tensor:
+    """``g.t().mm(xb)``: the split-K HIP kernels (``csrc/wgrad_splitk.hip``)
+    for the shapes their plan routes (contiguous, 16-byte aligned bf16 GPU
+    operands, a large batch), the GEMM library for everything else.
+    ``DE_WGRAD_SPLITK=0`` keeps every shape on the library.
+    """
+    if (g.is_cuda and g.dim() == 2 and xb.dim() == 2
+            and g.dtype == torch.bfloat16 and xb.dtype == torch.bfloat16
+            and g.is_contiguous() and xb.is_contiguous()
+            and g.data_ptr() % 16 == 0 and xb.data_ptr() % 16 == 0
+            and os.environ.get("DE_WGRAD_SPLITK", "1") != "0"
+            and _wgrad_routed(g.shape[0], g.shape[1], xb.shape[1])):
+        return _backend.ops().wgrad_splitk(g, xb)
+    return g.t().mm(xb)
+
+
 class _LinearReLU(torch.autograd.Function):
     """``relu(addmm(b, x, W^T))`` in bf16 for fp32 parameters.
 
     Issues exactly the casts and GEMM calls of autocast ``F.linear`` + ReLU
     and of their autograd backward (``addmm``; ``g.mm(W)``; ``g.t().mm(x)``),
     so the TunableOp selections in ``profiles/`` keep applying; only the
-    masking and the bias gradient differ (one kernel instead of two).
+    masking and the bias gradient differ (one kernel instead of two) and, at
+    the shapes ``weight_grad`` routes, the weight gradient.
     """
 
     @staticmethod
@@ -63,7 +90,7 @@ class _LinearReLU(torch.autograd.Function):
         gx = None
         if ctx.needs_input_grad[0]:
             gx = g.mm(wb).to(ctx.x_dtype)
-        gw = g.t().mm(xb)
+        gw = weight_grad(g, xb)
         # bf16 gradients of the fp32 parameters: the engine converts them
         return gx, gw, gb
 
