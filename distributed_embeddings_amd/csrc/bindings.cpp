@@ -762,18 +762,28 @@ torch::Tensor stochastic_round_bf16(torch::Tensor x, int64_t seed,
   return out;
 }
 
+// Shapes the interaction kernels take: the 32-row kernels serve F <= 32, the
+// 64-row kernels 33 <= F <= 64 at D <= 256 (their LDS block).
+static void check_dot_interact_shape(int64_t F, int64_t D) {
+  TORCH_CHECK(F >= 1 && D >= 32 && D % 32 == 0 &&
+                  (F <= 32 || (F <= 64 && D <= 256)),
+              "F<=32 and D%32==0, or F<=64, D%32==0 and D<=256 required "
+              "(got F=", F, ", D=", D, ")");
+}
+
 torch::Tensor dot_interact_fwd(torch::Tensor feats, int64_t out_w) {
   CHECK_CUDA(feats); CHECK_CONTIG(feats);
   TORCH_CHECK(feats.dtype() == torch::kBFloat16, "feats must be bf16");
   TORCH_CHECK(feats.dim() == 3, "feats must be [B, F, D]");
   const int64_t B = feats.size(0);
+  check_dot_interact_shape(feats.size(1), feats.size(2));
   const int F = (int)feats.size(1), D = (int)feats.size(2);
-  TORCH_CHECK(F <= 32 && D % 32 == 0, "F<=32 and D%32==0 required");
   const int tri_n = F * (F - 1) / 2;
   TORCH_CHECK(out_w >= tri_n + D, "out width too small");
   auto out = torch::empty({B, out_w}, feats.options());
-  launch_dot_interact_fwd(feats.data_ptr(), out.data_ptr(), B, F, D,
-                          (int)out_w, tri_n, current_stream());
+  (F <= 32 ? launch_dot_interact_fwd : launch_dot_interact_fwd64)(
+      feats.data_ptr(), out.data_ptr(), B, F, D, (int)out_w, tri_n,
+      current_stream());
   return out;
 }
 
@@ -795,16 +805,16 @@ torch::Tensor dot_interact_fwd_packed(torch::Tensor bottom,
   TORCH_CHECK(packed.size(sample_major ? 0 : 1) == B && packed.size(2) == D,
               "shape mismatch");
   TORCH_CHECK(perm.numel() == P, "perm must have P entries");
+  check_dot_interact_shape((int64_t)P + 1, bottom.size(1));
   const int F = P + 1;
-  TORCH_CHECK(F <= 32 && D % 32 == 0, "F<=32 and D%32==0 required");
   const int tri_n = F * (F - 1) / 2;
   TORCH_CHECK(out_w >= tri_n + D, "out width too small");
   const int64_t sb = sample_major ? P : 1;
   const int64_t sp = sample_major ? 1 : B;
   auto out = torch::empty({B, out_w}, bottom.options());
-  launch_dot_interact_fwd_packed(bottom.data_ptr(), packed.data_ptr(),
-                                 perm.data_ptr<int>(), out.data_ptr(), B, F, D,
-                                 (int)out_w, tri_n, sb, sp, current_stream());
+  (F <= 32 ? launch_dot_interact_fwd_packed : launch_dot_interact_fwd_packed64)(
+      bottom.data_ptr(), packed.data_ptr(), perm.data_ptr<int>(),
+      out.data_ptr(), B, F, D, (int)out_w, tri_n, sb, sp, current_stream());
   return out;
 }
 
@@ -820,23 +830,27 @@ std::vector<torch::Tensor> dot_interact_bwd_packed(torch::Tensor gout,
               bottom.dtype() == torch::kBFloat16 &&
               packed.dtype() == torch::kBFloat16, "bf16 required");
   TORCH_CHECK(perm.dtype() == torch::kInt32, "perm must be int32");
+  TORCH_CHECK(gout.dim() == 2 && bottom.dim() == 2 && packed.dim() == 3,
+              "gout [B,W], bottom [B,D], packed 3-D");
   const int64_t B = bottom.size(0);
   const int D = (int)bottom.size(1);
   const int P = (int)(sample_major ? packed.size(1) : packed.size(0));
   TORCH_CHECK(perm.numel() == P, "perm must have P entries");
   TORCH_CHECK(packed.size(sample_major ? 0 : 1) == B && packed.size(2) == D,
               "shape mismatch");
+  check_dot_interact_shape((int64_t)P + 1, bottom.size(1));
   const int F = P + 1;
   const int tri_n = F * (F - 1) / 2;
+  TORCH_CHECK(gout.size(0) == B && gout.size(1) >= tri_n + D,
+              "gout must be [B, >= F(F-1)/2 + D]");
   const int64_t sb = sample_major ? P : 1;
   const int64_t sp = sample_major ? 1 : B;
   auto gbottom = torch::empty_like(bottom);
   auto gpacked = torch::empty_like(packed);
-  launch_dot_interact_bwd_packed(gout.data_ptr(), bottom.data_ptr(),
-                                 packed.data_ptr(), perm.data_ptr<int>(),
-                                 gbottom.data_ptr(), gpacked.data_ptr(), B, F,
-                                 D, (int)gout.size(1), tri_n, sb, sp,
-                                 current_stream());
+  (F <= 32 ? launch_dot_interact_bwd_packed : launch_dot_interact_bwd_packed64)(
+      gout.data_ptr(), bottom.data_ptr(), packed.data_ptr(),
+      perm.data_ptr<int>(), gbottom.data_ptr(), gpacked.data_ptr(), B, F, D,
+      (int)gout.size(1), tri_n, sb, sp, current_stream());
   return {gbottom, gpacked};
 }
 
@@ -844,14 +858,19 @@ torch::Tensor dot_interact_bwd(torch::Tensor gout, torch::Tensor feats) {
   CHECK_CUDA(gout); CHECK_CUDA(feats);
   CHECK_CONTIG(gout); CHECK_CONTIG(feats);
   TORCH_CHECK(gout.dtype() == torch::kBFloat16 &&
-              feats.dtype() == torch::kBFloat16);
+              feats.dtype() == torch::kBFloat16, "bf16 required");
+  TORCH_CHECK(gout.dim() == 2 && feats.dim() == 3,
+              "gout [B,W], feats [B,F,D]");
   const int64_t B = feats.size(0);
+  check_dot_interact_shape(feats.size(1), feats.size(2));
   const int F = (int)feats.size(1), D = (int)feats.size(2);
   const int tri_n = F * (F - 1) / 2;
+  TORCH_CHECK(gout.size(0) == B && gout.size(1) >= tri_n + D,
+              "gout must be [B, >= F(F-1)/2 + D]");
   auto gfeats = torch::empty_like(feats);
-  launch_dot_interact_bwd(gout.data_ptr(), feats.data_ptr(),
-                          gfeats.data_ptr(), B, F, D, (int)gout.size(1), tri_n,
-                          current_stream());
+  (F <= 32 ? launch_dot_interact_bwd : launch_dot_interact_bwd64)(
+      gout.data_ptr(), feats.data_ptr(), gfeats.data_ptr(), B, F, D,
+      (int)gout.size(1), tri_n, current_stream());
   return gfeats;
 }
 

@@ -156,6 +156,24 @@ void launch_dot_interact_fwd(const void* feats, void* out, int64_t B, int F,
 void launch_dot_interact_bwd(const void* gout, const void* feats, void* gfeats,
                              int64_t B, int F, int D, int out_w, int tri_n,
                              hipStream_t stream);
+// The launchers above serve F <= 32 (D % 32 == 0); these serve 33 <= F <= 64
+// with D % 32 == 0 and D <= 256, and throw std::invalid_argument outside that.
+void launch_dot_interact_fwd_packed64(const void* bottom, const void* packed,
+                                      const int* perm, void* out, int64_t B,
+                                      int F, int D, int out_w, int tri_n,
+                                      int64_t sb, int64_t sp,
+                                      hipStream_t stream);
+void launch_dot_interact_bwd_packed64(const void* gout, const void* bottom,
+                                      const void* packed, const int* perm,
+                                      void* gbottom, void* gpacked, int64_t B,
+                                      int F, int D, int out_w, int tri_n,
+                                      int64_t sb, int64_t sp,
+                                      hipStream_t stream);
+void launch_dot_interact_fwd64(const void* feats, void* out, int64_t B, int F,
+                               int D, int out_w, int tri_n, hipStream_t stream);
+void launch_dot_interact_bwd64(const void* gout, const void* feats,
+                               void* gfeats, int64_t B, int F, int D,
+                               int out_w, int tri_n, hipStream_t stream);
 
 // mlp_ops.hip.  relu_bwd_bias_grad: grad_in = (y <= 0) ? 0 : grad_out and
 // bias_grad = bf16(column sums of grad_in), bf16 [B, N] with N % 8 == 0.

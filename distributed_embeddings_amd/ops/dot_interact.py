@@ -2,8 +2,10 @@
 
 Replaces the stack + bmm + tril-mask + concat chain of the reference
 (``examples/dlrm/utils.py:92-113``) with one MFMA kernel each direction
-(``csrc/dot_interact.hip``).  Falls back to plain torch ops off-GPU or for
-unsupported shapes (F > 32 or D % 32 != 0).
+(``csrc/dot_interact.hip``).  Falls back to plain torch ops off-GPU, for
+inputs that are not bf16, and for shapes the kernels do not take: they need
+D % 32 == 0 and either F <= 32, or F <= 64 with D <= 256 (F counts the
+bottom-MLP output as feature 0).
 """
 
 from typing import List
@@ -11,6 +13,13 @@ from typing import List
 import torch
 
 from . import _backend
+
+
+def kernel_shape_ok(f: int, d: int) -> bool:
+    """Whether the HIP kernels take ``f`` features of width ``d``."""
+    if d % 32 != 0:
+        return False
+    return f <= 32 or (f <= 64 and d <= 256)
 
 
 class _DotInteract(torch.autograd.Function):
@@ -74,8 +83,8 @@ def dot_interact_packed(packed: torch.Tensor, bottom_mlp_out: torch.Tensor,
     width = f * (f - 1) // 2 + d
     out_w = max(pad_to, width)
     if (packed.is_cuda and packed.dtype == torch.bfloat16
-            and bottom_mlp_out.dtype == torch.bfloat16 and f <= 32
-            and d % 32 == 0):
+            and bottom_mlp_out.dtype == torch.bfloat16
+            and kernel_shape_ok(f, d)):
         return _DotInteractPacked.apply(bottom_mlp_out.contiguous(),
                                         packed.contiguous(), perm, out_w,
                                         sample_major)
@@ -94,7 +103,7 @@ def dot_interact(emb_outs: List[torch.Tensor], bottom_mlp_out: torch.Tensor,
     f, d = feats.shape[1], feats.shape[2]
     width = f * (f - 1) // 2 + d
     out_w = max(pad_to, width)
-    if (feats.is_cuda and feats.dtype == torch.bfloat16 and f <= 32
-            and d % 32 == 0):
+    if (feats.is_cuda and feats.dtype == torch.bfloat16
+            and kernel_shape_ok(f, d)):
         return _DotInteract.apply(feats.contiguous(), out_w)
     return _torch_dot_interact(feats, out_w)
