@@ -904,6 +904,121 @@ std::vector<torch::Tensor> relu_bwd_bias_grad(torch::Tensor grad_out,
   return {grad_in, bias_grad};
 }
 
+#define CHECK_ALIGN16(x)                                                     \
+  TORCH_CHECK(reinterpret_cast<uintptr_t>((x).data_ptr()) % 16 == 0,         \
+              #x " must be 16-byte aligned")
+
+// Elementwise backward of one low-rank cross layer x_{l+1} = x0 * u + x_l
+// (mlp_ops.hip): gu = G * x0, gb = column sums of gu and, in place,
+// acc = (init ? 0 : acc) + G * u, from one pass.  Returns (gu, gb).  Outputs
+// and the fp32 partial slab come from the torch allocator and both launches
+// go on the current stream, so the op can be captured in a hipGraph.
+std::vector<torch::Tensor> cross_bwd(torch::Tensor G, torch::Tensor x0,
+                                     torch::Tensor u, torch::Tensor acc,
+                                     bool init) {
+  CHECK_CUDA(G); CHECK_CUDA(x0); CHECK_CUDA(u); CHECK_CUDA(acc);
+  CHECK_CONTIG(G); CHECK_CONTIG(x0); CHECK_CONTIG(u); CHECK_CONTIG(acc);
+  TORCH_CHECK(G.dtype() == torch::kBFloat16 &&
+              x0.dtype() == torch::kBFloat16 &&
+              u.dtype() == torch::kBFloat16 &&
+              acc.dtype() == torch::kBFloat16, "bf16 required");
+  TORCH_CHECK(G.dim() == 2 && G.sizes() == x0.sizes() &&
+              G.sizes() == u.sizes() && G.sizes() == acc.sizes(),
+              "G, x0, u and acc must be [B, N]");
+  TORCH_CHECK(G.device() == x0.device() && G.device() == u.device() &&
+              G.device() == acc.device(), "operands must share a device");
+  const int64_t B = G.size(0);
+  const int64_t N = G.size(1);
+  TORCH_CHECK(N % 8 == 0 && N < (int64_t(1) << 31), "N % 8 == 0 required");
+  CHECK_ALIGN16(G); CHECK_ALIGN16(x0); CHECK_ALIGN16(u); CHECK_ALIGN16(acc);
+  auto gu = torch::empty_like(G);
+  if (B == 0 || N == 0) {
+    return {gu, torch::zeros({N}, G.options())};
+  }
+  TORCH_CHECK(acc.data_ptr() != G.data_ptr() &&
+              acc.data_ptr() != x0.data_ptr() &&
+              acc.data_ptr() != u.data_ptr(),
+              "acc is written in place and must not alias an input");
+  auto gb = torch::empty({N}, G.options());
+  int64_t rows_per_chunk = 0, num_chunks = 0;
+  relu_bwd_bias_grad_plan(B, (int)N, &rows_per_chunk, &num_chunks);
+  auto slab = torch::empty({num_chunks, N},
+                           G.options().dtype(torch::kFloat32));
+  launch_cross_bwd(G.data_ptr(), x0.data_ptr(), u.data_ptr(), acc.data_ptr(),
+                   init, gu.data_ptr(), slab.data_ptr<float>(), gb.data_ptr(),
+                   B, (int)N, rows_per_chunk, num_chunks, current_stream());
+  return {gu, gb};
+}
+
+// Shapes of the cross interaction's input assembly: bottom [B, D], packed
+// [P, B, D] (feature-major) or [B, P, D] (sample-major), x0 [B, (P+1)*D].
+static void check_cross_concat_shape(int64_t B, int64_t P, int64_t D) {
+  TORCH_CHECK(P >= 1 && D >= 8 && D % 8 == 0,
+              "P >= 1 and D % 8 == 0 required (got P=", P, ", D=", D, ")");
+  // a block walks 16 rows of x0 with 32-bit indices
+  TORCH_CHECK((P + 1) * D < (int64_t(1) << 27), "row of x0 too wide");
+  TORCH_CHECK(B >= 0, "negative batch");
+}
+
+torch::Tensor cross_concat_fwd(torch::Tensor bottom, torch::Tensor packed,
+                               torch::Tensor perm, bool sample_major) {
+  CHECK_CUDA(bottom); CHECK_CUDA(packed); CHECK_CUDA(perm);
+  CHECK_CONTIG(bottom); CHECK_CONTIG(packed); CHECK_CONTIG(perm);
+  TORCH_CHECK(bottom.dtype() == torch::kBFloat16 &&
+              packed.dtype() == torch::kBFloat16, "bf16 required");
+  TORCH_CHECK(perm.dtype() == torch::kInt32, "perm must be int32");
+  TORCH_CHECK(bottom.dim() == 2 && packed.dim() == 3,
+              "bottom [B,D], packed 3-D");
+  TORCH_CHECK(bottom.device() == packed.device() &&
+              bottom.device() == perm.device(),
+              "operands must share a device");
+  const int64_t B = bottom.size(0);
+  const int64_t D = bottom.size(1);
+  const int64_t P = sample_major ? packed.size(1) : packed.size(0);
+  TORCH_CHECK(packed.size(sample_major ? 0 : 1) == B && packed.size(2) == D,
+              "shape mismatch");
+  TORCH_CHECK(perm.numel() == P, "perm must have P entries");
+  check_cross_concat_shape(B, P, D);
+  CHECK_ALIGN16(bottom); CHECK_ALIGN16(packed);
+  const int64_t sb = sample_major ? P : 1;
+  const int64_t sp = sample_major ? 1 : B;
+  auto x0 = torch::empty({B, (P + 1) * D}, bottom.options());
+  launch_cross_concat_fwd(bottom.data_ptr(), packed.data_ptr(),
+                          perm.data_ptr<int>(), x0.data_ptr(), B, (int)P,
+                          (int)D, sb, sp, current_stream());
+  return x0;
+}
+
+// (gbottom [B, D], gpacked in packed's layout) from gx0 [B, (P+1)*D]; perm
+// has to be a permutation of [0, P).
+std::vector<torch::Tensor> cross_concat_bwd(torch::Tensor gx0,
+                                            torch::Tensor perm,
+                                            bool sample_major) {
+  CHECK_CUDA(gx0); CHECK_CUDA(perm);
+  CHECK_CONTIG(gx0); CHECK_CONTIG(perm);
+  TORCH_CHECK(gx0.dtype() == torch::kBFloat16, "bf16 required");
+  TORCH_CHECK(perm.dtype() == torch::kInt32, "perm must be int32");
+  TORCH_CHECK(gx0.dim() == 2 && perm.dim() == 1 && perm.numel() >= 1,
+              "gx0 [B, (P+1)*D], perm [P]");
+  TORCH_CHECK(gx0.device() == perm.device(), "operands must share a device");
+  const int64_t B = gx0.size(0);
+  const int64_t P = perm.numel();
+  TORCH_CHECK(gx0.size(1) % (P + 1) == 0,
+              "gx0 width must be a multiple of P + 1");
+  const int64_t D = gx0.size(1) / (P + 1);
+  check_cross_concat_shape(B, P, D);
+  CHECK_ALIGN16(gx0);
+  const int64_t sb = sample_major ? P : 1;
+  const int64_t sp = sample_major ? 1 : B;
+  auto gbottom = torch::empty({B, D}, gx0.options());
+  auto gpacked = sample_major ? torch::empty({B, P, D}, gx0.options())
+                              : torch::empty({P, B, D}, gx0.options());
+  launch_cross_concat_bwd(gx0.data_ptr(), perm.data_ptr<int>(),
+                          gbottom.data_ptr(), gpacked.data_ptr(), B, (int)P,
+                          (int)D, sb, sp, current_stream());
+  return {gbottom, gpacked};
+}
+
 // Weight gradient of a Linear layer, gw = bf16(g^T x) with fp32 accumulation
 // (wgrad_splitk.hip).  The slab comes from the torch allocator and both
 // launches go on the current stream: capturable.  splitk > 0 and tile >= 0
@@ -1028,6 +1143,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("relu_bwd_bias_grad", &relu_bwd_bias_grad,
         "ReLU backward + bias gradient in one pass -> (grad_in, bias_grad) "
         "(gfx950)");
+  m.def("cross_bwd", &cross_bwd,
+        "low-rank cross layer backward: gu = G * x0, its column sum, and "
+        "acc (+)= G * u in place, one pass -> (gu, gb) (gfx950)",
+        pybind11::arg("G"), pybind11::arg("x0"), pybind11::arg("u"),
+        pybind11::arg("acc"), pybind11::arg("init"));
+  m.def("cross_concat_fwd", &cross_concat_fwd,
+        "x0 = [bottom | packed rows in perm order] (gfx950)",
+        pybind11::arg("bottom"), pybind11::arg("packed"),
+        pybind11::arg("perm"), pybind11::arg("sample_major"));
+  m.def("cross_concat_bwd", &cross_concat_bwd,
+        "gradient of x0 -> (gbottom, gpacked) (gfx950)",
+        pybind11::arg("gx0"), pybind11::arg("perm"),
+        pybind11::arg("sample_major"));
   m.def("wgrad_splitk", &wgrad_splitk,
         "Linear weight gradient bf16(g^T x), split-K (MFMA bf16, gfx950)",
         pybind11::arg("g"), pybind11::arg("x"), pybind11::arg("splitk") = 0,

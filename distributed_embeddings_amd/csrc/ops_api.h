@@ -185,6 +185,31 @@ void launch_relu_bwd_bias_grad(const void* grad_out, const void* y,
                                int64_t B, int N, int64_t rows_per_chunk,
                                int64_t num_chunks, hipStream_t stream);
 
+// mlp_ops.hip.  cross_bwd, the elementwise backward of one low-rank cross
+// layer x_{l+1} = x0 * u + x_l, all bf16 [B, N] with N % 8 == 0 and 16-byte
+// aligned: gu = bf16(gout * x0), bias_grad = bf16(column sums of gu) and, in
+// place, acc = bf16((init ? 0 : acc) + gout * u) formed in fp32.  init never
+// reads acc.  Slab [num_chunks, N] fp32 from relu_bwd_bias_grad_plan.
+void launch_cross_bwd(const void* gout, const void* x0, const void* u,
+                      void* acc, bool init, void* gu, float* slab,
+                      void* bias_grad, int64_t B, int N,
+                      int64_t rows_per_chunk, int64_t num_chunks,
+                      hipStream_t stream);
+
+// cross_ops.hip.  x0 [B, (P+1)*D] = [bottom | packed rows in perm order]:
+// x0[b, 0:D] = bottom[b], x0[b, f*D:(f+1)*D] = packed row perm[f-1] of sample
+// b, at element offset (b*sb + perm[f-1]*sp)*D as in the packed dot
+// interaction.  bf16, D % 8 == 0, 16-byte aligned.  The backward splits gx0
+// into gbottom and gpacked; perm has to be a permutation of [0, P) for it to
+// cover gpacked, and an entry outside [0, P) is skipped (zeros in x0).
+void launch_cross_concat_fwd(const void* bottom, const void* packed,
+                             const int* perm, void* x0, int64_t B, int P,
+                             int D, int64_t sb, int64_t sp,
+                             hipStream_t stream);
+void launch_cross_concat_bwd(const void* gx0, const int* perm, void* gbottom,
+                             void* gpacked, int64_t B, int P, int D,
+                             int64_t sb, int64_t sp, hipStream_t stream);
+
 // wgrad_splitk.hip.  gw [M, N] = bf16(g^T x) for bf16 g [K, M], x [K, N], fp32
 // accumulation, one rounding: split-K partial products into the fp32 slab
 // [splitk, M, np], then a fixed-order sum.  M % 8 == 0; N % 8 == 0 or N <= 16.

@@ -13,6 +13,11 @@ ReLU backward and the bias gradient run as one kernel); the pairwise-dot
 interaction runs as one fused MFMA kernel each direction
 (``csrc/dot_interact.hip``, dispatched by ``ops/dot_interact.py``; plain
 bmm fallback when the shape or dtype gate fails).
+
+``interaction="cross"`` builds DLRM-DCNv2 instead: the same tables and MLPs
+around a low-rank cross network over the concatenated features
+(``ops/cross.py``), beyond the reference, which ships the dot interaction
+only.
 """
 
 import math
@@ -23,6 +28,7 @@ import torch
 from torch import nn
 
 from ..layers.embedding import Embedding, scaled_uniform_init
+from ..ops.cross import LowRankCrossNet, concat_packed
 from ..ops.dot_interact import dot_interact as fused_dot_interact
 from ..ops.dot_interact import dot_interact_packed
 from ..ops.mlp import MLP
@@ -75,6 +81,9 @@ class DLRM(nn.Module):
       num_numerical: dense feature count (13 for Criteo).
       strategy: DistributedEmbedding placement strategy.
       dp_input: data-parallel input mode (see DistributedEmbedding).
+      interaction: "dot" (pairwise dot products, the default) or "cross"
+        (DCN-v2 low-rank cross network, DLRM-DCNv2).
+      cross_layers / cross_rank: depth and rank of the cross network.
     """
 
     def __init__(
@@ -89,8 +98,15 @@ class DLRM(nn.Module):
         column_slice_threshold: Optional[int] = None,
         data_parallel_threshold: Optional[int] = None,
         table_dtype: torch.dtype = torch.float32,
+        interaction: str = "dot",
+        cross_layers: int = 3,
+        cross_rank: int = 512,
     ):
         super().__init__()
+        if interaction not in ("dot", "cross"):
+            raise ValueError(
+                f"interaction must be 'dot' or 'cross', got {interaction!r}")
+        self.interaction = interaction
         self.table_sizes = list(table_sizes)
         self.embedding_dim = embedding_dim
         self.distributed = comm.world_size() > 1
@@ -102,10 +118,16 @@ class DLRM(nn.Module):
             bottom_mlp_dims[-1] = embedding_dim
         self.bottom_mlp = _mlp(bottom_mlp_dims, num_numerical, final_linear=False)
         num_feats = len(table_sizes) + 1
-        interact_dim = num_feats * (num_feats - 1) // 2 + bottom_mlp_dims[-1]
+        if interaction == "cross":
+            # the top MLP reads x_L: 27 * 128 = 3456 for Criteo, no padding
+            interact_dim = num_feats * embedding_dim
+        else:
+            interact_dim = num_feats * (num_feats - 1) // 2 + bottom_mlp_dims[-1]
         # zero-pad to a multiple of 64 for MFMA-friendly GEMM K (479 -> 512)
         self.interact_pad = ((interact_dim + 63) // 64) * 64
         self.top_mlp = _mlp(top_mlp_dims, self.interact_pad, final_linear=True)
+        self.cross = LowRankCrossNet(interact_dim, cross_layers, cross_rank) \
+            if interaction == "cross" else None
 
         from ..parallel.strategy import TableConfig
         tables = [
@@ -140,6 +162,21 @@ class DLRM(nn.Module):
             return self.embeddings.local_input_ids()
         return list(range(len(self.table_sizes)))
 
+    def _cross_interact(self, x0: torch.Tensor) -> torch.Tensor:
+        x = self.cross(x0)
+        if self.interact_pad > x.shape[1]:
+            x = nn.functional.pad(x, (0, self.interact_pad - x.shape[1]))
+        return x
+
+    def _interact_packed(self, packed: torch.Tensor, bottom: torch.Tensor,
+                         sample_major: bool) -> torch.Tensor:
+        if self.cross is not None:
+            return self._cross_interact(concat_packed(
+                packed, bottom, self._dot_perm, sample_major=sample_major))
+        return dot_interact_packed(packed, bottom, self._dot_perm,
+                                   pad_to=self.interact_pad,
+                                   sample_major=sample_major)
+
     def forward(self, numerical: torch.Tensor,
                 cat_features: Sequence[torch.Tensor]) -> torch.Tensor:
         cats = list(cat_features)
@@ -172,19 +209,18 @@ class DLRM(nn.Module):
             main.wait_stream(self._emb_stream)
             if not torch.cuda.is_current_stream_capturing():
                 packed.record_stream(main)
-            x = dot_interact_packed(packed, bottom, self._dot_perm,
-                                    pad_to=self.interact_pad,
-                                    sample_major=smaj)
+            x = self._interact_packed(packed, bottom, smaj)
             return self.top_mlp(x)
         bottom = self.bottom_mlp(numerical)
         if use_packed:
             packed, smaj = self.embeddings.forward_packed(
                 cats, output_dtype=bottom.dtype, async_handle=handle)
-            x = dot_interact_packed(packed, bottom, self._dot_perm,
-                                    pad_to=self.interact_pad,
-                                    sample_major=smaj)
+            x = self._interact_packed(packed, bottom, smaj)
         else:
             emb = self.embeddings(cats, output_dtype=bottom.dtype,
                                   async_handle=handle)
-            x = fused_dot_interact(emb, bottom, pad_to=self.interact_pad)
+            if self.cross is not None:
+                x = self._cross_interact(torch.cat([bottom] + list(emb), 1))
+            else:
+                x = fused_dot_interact(emb, bottom, pad_to=self.interact_pad)
         return self.top_mlp(x)

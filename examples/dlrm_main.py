@@ -6,6 +6,8 @@ training with DistributedEmbedding, custom train step with dp-grad averaging,
 first-step parameter broadcast, AUC evaluation with allgathered predictions,
 embedding dump via get_weights, warmup + polynomial-decay LR schedule, and a
 binary Criteo dataset reader (or synthetic data when no dataset is given).
+Beyond it, ``--interaction cross`` trains DLRM-DCNv2: the same tables and
+MLPs around a DCN-v2 low-rank cross network.
 
 Launch (one process per GPU):
   torchrun --standalone --local-addr 127.0.0.1 --nproc-per-node 8 \
@@ -59,6 +61,11 @@ def parse_args():
                    help="in-backward fused SGD on the model-parallel tables "
                         "(no grad tensors, no host syncs; the schedule "
                         "updates the device-resident lr)")
+    p.add_argument("--interaction", choices=("dot", "cross"), default="dot",
+                   help="dot: pairwise dot products (DLRM); cross: DCN-v2 "
+                        "low-rank cross network (DLRM-DCNv2)")
+    p.add_argument("--cross-layers", type=int, default=3)
+    p.add_argument("--cross-rank", type=int, default=512)
     return p.parse_args()
 
 
@@ -107,7 +114,9 @@ def main():
         table_sizes = [min(s, args.table_size_cap) for s in table_sizes]
     with torch.device(device):
         model = DLRM(table_sizes, embedding_dim=args.embedding_dim,
-                     strategy=args.dist_strategy, dp_input=args.dp_input or world == 1)
+                     strategy=args.dist_strategy, dp_input=args.dp_input or world == 1,
+                     interaction=args.interaction,
+                     cross_layers=args.cross_layers, cross_rank=args.cross_rank)
 
     local_bs = args.batch_size // world
     feature_ids = model.local_cat_feature_ids()

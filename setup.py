@@ -21,6 +21,7 @@ ext = CUDAExtension(
         "distributed_embeddings_amd/csrc/dot_interact.hip",
         "distributed_embeddings_amd/csrc/radix_sort.hip",
         "distributed_embeddings_amd/csrc/mlp_ops.hip",
+        "distributed_embeddings_amd/csrc/cross_ops.hip",
         "distributed_embeddings_amd/csrc/wgrad_splitk.hip",
     ],
     extra_compile_args={
