@@ -9,8 +9,10 @@ embedding hot ops, RCCL collectives over the 8-GPU xGMI full mesh via
 Public API (parity: reference ``distributed_embeddings/__init__.py:17-27``):
 """
 
-from .ops.embedding_lookup import (Ragged, dequantize_rowwise_int8,
-                                   embedding_lookup, quantize_rowwise_int8,
+from .ops.embedding_lookup import (Ragged, dequantize_rowwise_int4,
+                                   dequantize_rowwise_int8, embedding_lookup,
+                                   quantize_rowwise_int4,
+                                   quantize_rowwise_int8,
                                    quantized_embedding_lookup, row_to_split,
                                    stochastic_round_bf16)
 from .layers.embedding import ConcatOneHotEmbedding, Embedding, scaled_uniform_init
@@ -37,6 +39,8 @@ __all__ = [
     "row_to_split",
     "quantize_rowwise_int8",
     "dequantize_rowwise_int8",
+    "quantize_rowwise_int4",
+    "dequantize_rowwise_int4",
     "quantized_embedding_lookup",
     "stochastic_round_bf16",
     "Embedding",

@@ -164,19 +164,38 @@ torch::Tensor csr_lookup_forward(torch::Tensor params, torch::Tensor values,
   TORCH_CHECK(reinterpret_cast<uintptr_t>((x).data_ptr()) % 4 == 0,          \
               #x " must be 4-byte aligned")
 
-torch::Tensor csr_lookup_forward_q8(torch::Tensor packed, torch::Tensor values,
-                                    torch::Tensor row_splits, bool mean,
+// int4 row-wise quantized table: uint8 [vocab, width / 2 + 4] (width / 2
+// bytes of nibbles, fp16 scale, fp16 bias per row), width a positive
+// multiple of 8.
+#define CHECK_Q4_PACKED(x)                                                   \
+  CHECK_CUDA(x); CHECK_CONTIG(x);                                            \
+  TORCH_CHECK((x).dtype() == torch::kUInt8, #x " must be uint8");            \
+  TORCH_CHECK((x).dim() == 2 && (x).size(1) >= 8 &&                          \
+                  ((x).size(1) - 4) % 4 == 0,                                \
+              #x " must be [vocab, width / 2 + 4] with width a positive "    \
+                 "multiple of 8");                                           \
+  TORCH_CHECK(reinterpret_cast<uintptr_t>((x).data_ptr()) % 4 == 0,          \
+              #x " must be 4-byte aligned")
+
+using PackedForwardLauncher = decltype(&launch_csr_lookup_forward_q8);
+
+// The forward from a checked packed table of logical width `width`.
+torch::Tensor packed_lookup_forward(PackedForwardLauncher launch,
+                                    const torch::Tensor& packed, int width,
+                                    const torch::Tensor& values,
+                                    const torch::Tensor& row_splits, bool mean,
                                     bool out_bf16,
-                                    std::optional<torch::Tensor> per_id_w) {
-  CHECK_Q8_PACKED(packed);
+                                    const std::optional<torch::Tensor>& per_id_w) {
   CHECK_CUDA(values); CHECK_CUDA(row_splits);
   CHECK_CONTIG(values); CHECK_CONTIG(row_splits);
   TORCH_CHECK(values.dtype() == torch::kInt64, "values must be int64");
   TORCH_CHECK(row_splits.dtype() == torch::kInt64, "row_splits must be int64");
+  TORCH_CHECK(values.device() == packed.device() &&
+                  row_splits.device() == packed.device(),
+              "packed, values and row_splits must be on one device");
   const float* w_ptr = per_id_w_ptr(per_id_w, values);
   const int64_t num_rows = row_splits.numel() - 1;
   const int64_t vocab = packed.size(0);
-  const int width = (int)packed.size(1) - 8;
   const auto opts = packed.options().dtype(out_bf16 ? torch::kBFloat16
                                                     : torch::kFloat32);
   // an empty table has no row to read: every id is out of range
@@ -190,17 +209,34 @@ torch::Tensor csr_lookup_forward_q8(torch::Tensor packed, torch::Tensor values,
     auto long_count = torch::empty({1}, values.options().dtype(torch::kInt32));
     auto work_items = torch::empty({nnz_in / 64 + 64}, values.options());
     auto n_work = torch::empty({1}, values.options().dtype(torch::kInt32));
-    launch_csr_lookup_forward_q8(packed.data_ptr(),
-                                 values.data_ptr<int64_t>(),
-                                 row_splits.data_ptr<int64_t>(), w_ptr,
-                                 out.data_ptr(), out_bf16, num_rows, nnz_in,
-                                 vocab, width, mean,
-                                 long_rows.data_ptr<int64_t>(),
-                                 long_count.data_ptr<int32_t>(),
-                                 work_items.data_ptr<int64_t>(),
-                                 n_work.data_ptr<int32_t>(), current_stream());
+    launch(packed.data_ptr(), values.data_ptr<int64_t>(),
+           row_splits.data_ptr<int64_t>(), w_ptr, out.data_ptr(), out_bf16,
+           num_rows, nnz_in, vocab, width, mean,
+           long_rows.data_ptr<int64_t>(), long_count.data_ptr<int32_t>(),
+           work_items.data_ptr<int64_t>(), n_work.data_ptr<int32_t>(),
+           current_stream());
   }
   return out;
+}
+
+torch::Tensor csr_lookup_forward_q8(torch::Tensor packed, torch::Tensor values,
+                                    torch::Tensor row_splits, bool mean,
+                                    bool out_bf16,
+                                    std::optional<torch::Tensor> per_id_w) {
+  CHECK_Q8_PACKED(packed);
+  return packed_lookup_forward(&launch_csr_lookup_forward_q8, packed,
+                               (int)packed.size(1) - 8, values, row_splits,
+                               mean, out_bf16, per_id_w);
+}
+
+torch::Tensor csr_lookup_forward_q4(torch::Tensor packed, torch::Tensor values,
+                                    torch::Tensor row_splits, bool mean,
+                                    bool out_bf16,
+                                    std::optional<torch::Tensor> per_id_w) {
+  CHECK_Q4_PACKED(packed);
+  return packed_lookup_forward(&launch_csr_lookup_forward_q4, packed,
+                               2 * ((int)packed.size(1) - 4), values,
+                               row_splits, mean, out_bf16, per_id_w);
 }
 
 torch::Tensor quantize_rows_q8(torch::Tensor weight) {
@@ -233,6 +269,41 @@ torch::Tensor dequantize_rows_q8(torch::Tensor packed) {
   auto out = torch::empty({n, width},
                           packed.options().dtype(torch::kFloat32));
   launch_dequantize_rows_q8(packed.data_ptr(), out.data_ptr<float>(), n, width,
+                            current_stream());
+  return out;
+}
+
+torch::Tensor quantize_rows_q4(torch::Tensor weight) {
+  CHECK_CUDA(weight); CHECK_CONTIG(weight);
+  TORCH_CHECK(weight.dtype() == torch::kFloat32 ||
+                  weight.dtype() == torch::kBFloat16,
+              "weight must be fp32 or bf16");
+  TORCH_CHECK(weight.dim() == 2 && weight.size(1) >= 8 &&
+                  weight.size(1) % 8 == 0,
+              "weight must be [n, width] with width a positive multiple of "
+              "8 (the 4-bit layout itself only needs an even width), got "
+              "width ", weight.dim() == 2 ? weight.size(1) : -1);
+  // a lane loads its eight columns four at a time: 16 bytes of fp32, 8 of bf16
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(weight.data_ptr()) %
+                      (4 * weight.element_size()) == 0,
+              "weight must be aligned to four of its elements");
+  const int64_t n = weight.size(0);
+  const int width = (int)weight.size(1);
+  auto packed = torch::empty({n, width / 2 + 4},
+                             weight.options().dtype(torch::kUInt8));
+  launch_quantize_rows_q4(weight.data_ptr(),
+                          weight.dtype() == torch::kBFloat16,
+                          packed.data_ptr(), n, width, current_stream());
+  return packed;
+}
+
+torch::Tensor dequantize_rows_q4(torch::Tensor packed) {
+  CHECK_Q4_PACKED(packed);
+  const int64_t n = packed.size(0);
+  const int width = 2 * ((int)packed.size(1) - 4);
+  auto out = torch::empty({n, width},
+                          packed.options().dtype(torch::kFloat32));
+  launch_dequantize_rows_q4(packed.data_ptr(), out.data_ptr<float>(), n, width,
                             current_stream());
   return out;
 }
@@ -1079,6 +1150,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("weight"));
   m.def("dequantize_rows_q8", &dequantize_rows_q8,
         "int8 row-wise packed [n, width + 8] -> fp32 [n, width] (gfx950)",
+        pybind11::arg("packed"));
+  m.def("csr_lookup_forward_q4", &csr_lookup_forward_q4,
+        "CSR gather-reduce from an int4 row-wise quantized table (gfx950)",
+        pybind11::arg("packed"), pybind11::arg("values"),
+        pybind11::arg("row_splits"), pybind11::arg("mean"),
+        pybind11::arg("out_bf16") = false,
+        pybind11::arg("per_id_w") = pybind11::none());
+  m.def("quantize_rows_q4", &quantize_rows_q4,
+        "fp32/bf16 [n, width] -> int4 row-wise packed [n, width / 2 + 4] "
+        "(gfx950)",
+        pybind11::arg("weight"));
+  m.def("dequantize_rows_q4", &dequantize_rows_q4,
+        "int4 row-wise packed [n, width / 2 + 4] -> fp32 [n, width] (gfx950)",
         pybind11::arg("packed"));
   m.def("csr_lookup_backward", &csr_lookup_backward,
         "sparse backward: sort + unique + segmented sum (gfx950)",

@@ -15,6 +15,9 @@
 //     forward from int8 row-wise quantized tables (width bytes + fp32 scale +
 //     fp32 bias per row, inference only): the wide and long kernels above
 //     instantiated on q8_t, plus the device-side quantizer and its inverse.
+//   * csr_lookup_forward_q4 / quantize_rows_q4 / dequantize_rows_q4 — the
+//     same again for int4 row-wise tables in FBGEMM's fused 4-bit layout
+//     (width / 2 bytes of nibbles + fp16 scale + fp16 bias per row), on q4_t.
 //   * row_to_split        — COO rows -> CSR splits by per-row binary search
 //     (K4 equivalent).
 //   * csr_lookup_backward — rowid expansion + packed (id<<32|pos) keys-only
@@ -110,6 +113,21 @@ __device__ __forceinline__ void pt_store2(bf16_t* p, const float* v) {
   s.y = *reinterpret_cast<short*>(&h1);
   *reinterpret_cast<short2*>(p) = s;
 }
+// 8 contiguous elements (int4 tables): two 16-B stores of fp32, one of bf16
+__device__ __forceinline__ void pt_store8(float* p, const float* v) {
+  pt_store4(p, v);
+  pt_store4(p + 4, v + 4);
+}
+__device__ __forceinline__ void pt_store8(bf16_t* p, const float* v) {
+  unsigned int d[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    __hip_bfloat16 lo(v[2 * j]), hi(v[2 * j + 1]);
+    d[j] = (unsigned int)*reinterpret_cast<unsigned short*>(&lo) |
+           ((unsigned int)*reinterpret_cast<unsigned short*>(&hi) << 16);
+  }
+  *reinterpret_cast<uint4*>(p) = make_uint4(d[0], d[1], d[2], d[3]);
+}
 // VEC (4, 2 or 1) contiguous elements with the widest matching access
 template <int VEC, typename T>
 __device__ __forceinline__ void pt_loadv(const T* p, float* o) {
@@ -117,9 +135,11 @@ __device__ __forceinline__ void pt_loadv(const T* p, float* o) {
   else if constexpr (VEC == 2) pt_load2(p, o);
   else o[0] = pt_load(p);
 }
+// stores also take VEC == 8
 template <int VEC, typename T>
 __device__ __forceinline__ void pt_storev(T* p, const float* v) {
-  if constexpr (VEC == 4) pt_store4(p, v);
+  if constexpr (VEC == 8) pt_store8(p, v);
+  else if constexpr (VEC == 4) pt_store4(p, v);
   else if constexpr (VEC == 2) pt_store2(p, v);
   else pt_store(p, v[0]);
 }
@@ -390,6 +410,111 @@ __device__ __forceinline__ void wide_accumulate(
     ab += ok ? wk * bi : 0.f;
 #pragma unroll
     for (int v = 0; v < VEC; ++v) aq[v] += ws * q8_byte(q, v);
+  }
+#pragma unroll
+  for (int v = 0; v < VEC; ++v) acc[v] = aq[v] + ab;
+}
+
+// int4 row-wise quantized rows (inference tables): a row of the packed
+// [vocab, width / 2 + 4] byte table is width / 2 bytes of nibbles (column 2j
+// in the low nibble of byte j, column 2j + 1 in the high one), then fp16
+// scale, then fp16 bias, and stands for scale * q[c] + bias.  width % 8 == 0,
+// so a lane's dword is eight whole columns — column col0 + v is bits
+// [4v, 4v + 4) — and the row stride and the scale/bias dword are 4-byte
+// aligned.
+struct q4_t { unsigned char b; };
+
+#define Q4_TAIL 4  // bytes of scale + bias behind the nibbles
+
+__device__ __forceinline__ const unsigned char* q4_row(const q4_t* src,
+                                                       int64_t i, int width) {
+  return reinterpret_cast<const unsigned char*>(src) +
+         i * (int64_t)(width / 2 + Q4_TAIL);
+}
+__device__ __forceinline__ unsigned int q4_load8(const unsigned char* row,
+                                                 int col0) {
+  return *reinterpret_cast<const unsigned int*>(row + col0 / 2);
+}
+// scale (low half) and bias (high half) as stored: one dword
+__device__ __forceinline__ unsigned int q4_tail(const unsigned char* row,
+                                                int width) {
+  return *reinterpret_cast<const unsigned int*>(row + width / 2);
+}
+__device__ __forceinline__ float half_bits_to_float(unsigned int h) {
+  return (float)__builtin_bit_cast(_Float16, (unsigned short)h);
+}
+__device__ __forceinline__ float q4_scale(unsigned int tail) {
+  return half_bits_to_float(tail & 0xffffu);
+}
+__device__ __forceinline__ float q4_bias(unsigned int tail) {
+  return half_bits_to_float(tail >> 16);
+}
+// the eight columns of a dword as floats (0..15, exact): the even columns
+// are the bytes of q & 0x0f0f0f0f, the odd ones those of (q >> 4) & ...
+__device__ __forceinline__ void q4_unpack8(unsigned int q, float* f) {
+  const unsigned int even = q & 0x0f0f0f0fu, odd = (q >> 4) & 0x0f0f0f0fu;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    f[2 * j] = (float)((even >> (8 * j)) & 0xffu);
+    f[2 * j + 1] = (float)((odd >> (8 * j)) & 0xffu);
+  }
+}
+
+// The int4 wide gather-accumulate: the int8 overload's shape with one dword
+// of eight columns (VEC == 8) per lane and scale and bias from one dword —
+// bias factored out of the column sum, an id outside [0, vocab) pointed at
+// row 0 with both coefficients zeroed (the launcher guarantees vocab > 0),
+// four id -> row chains in flight, terms added in k order, fp32 throughout.
+template <int VEC, bool HAS_W, bool CHECK>
+__device__ __forceinline__ void wide_accumulate(
+    const q4_t* __restrict__ src, const int64_t* __restrict__ idx,
+    const float* __restrict__ w, int64_t vocab, int width, int col0,
+    int64_t ks, int64_t ke, float* acc /* size VEC */) {
+  static_assert(VEC == 8, "an int4 lane owns one dword of eight columns");
+  constexpr int UNROLL = 4;
+  float aq[VEC];
+#pragma unroll
+  for (int v = 0; v < VEC; ++v) aq[v] = 0.f;
+  float ab = 0.f;
+  int64_t k = ks;
+  for (; k + UNROLL <= ke; k += UNROLL) {
+    int64_t i[UNROLL];
+    bool ok[UNROLL];
+    unsigned int q[UNROLL], tail[UNROLL];
+#pragma unroll
+    for (int u = 0; u < UNROLL; ++u) i[u] = idx[k + u];
+#pragma unroll
+    for (int u = 0; u < UNROLL; ++u) {
+      ok[u] = !CHECK || (i[u] >= 0 && i[u] < vocab);
+      const unsigned char* row = q4_row(src, ok[u] ? i[u] : 0, width);
+      q[u] = q4_load8(row, col0);
+      tail[u] = q4_tail(row, width);
+    }
+#pragma unroll
+    for (int u = 0; u < UNROLL; ++u) {
+      const float wk = HAS_W ? w[k + u] : 1.f;
+      const float ws = ok[u] ? wk * q4_scale(tail[u]) : 0.f;
+      ab += ok[u] ? wk * q4_bias(tail[u]) : 0.f;
+      float f[VEC];
+      q4_unpack8(q[u], f);
+#pragma unroll
+      for (int v = 0; v < VEC; ++v) aq[v] += ws * f[v];
+    }
+  }
+  for (; k < ke; ++k) {
+    const int64_t i = idx[k];
+    const bool ok = !CHECK || (i >= 0 && i < vocab);
+    const unsigned char* row = q4_row(src, ok ? i : 0, width);
+    // both loads before the selects, as in the int8 overload
+    const unsigned int q = q4_load8(row, col0);
+    const unsigned int tail = q4_tail(row, width);
+    const float wk = HAS_W ? w[k] : 1.f;
+    const float ws = ok ? wk * q4_scale(tail) : 0.f;
+    ab += ok ? wk * q4_bias(tail) : 0.f;
+    float f[VEC];
+    q4_unpack8(q, f);
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) aq[v] += ws * f[v];
   }
 #pragma unroll
   for (int v = 0; v < VEC; ++v) acc[v] = aq[v] + ab;
@@ -928,9 +1053,13 @@ void launch_csr_lookup_forward(const void* params, bool params_bf16,
 // at width 4, 2 at width 128), the column loop runs from width 260 on, and
 // the long-row list, its expansion and the atomic combine are the fp32
 // tables' own.  vocab must be > 0 (see the q8_t wide_accumulate).
-template <typename OT>
-static void launch_csr_lookup_forward_q8_t(
-    const q8_t* params, const int64_t* values, const int64_t* splits,
+//
+// int4 tables (QT = q4_t, VEC = 8) run the same two kernels with
+// tile_w = pow2(width / 8) lanes per row: 64 rows per wave at width 8, 4 at
+// width 128, and the column loop from width 520 on.
+template <int VEC, typename QT, typename OT>
+static void launch_csr_lookup_forward_packed_t(
+    const QT* params, const int64_t* values, const int64_t* splits,
     const float* per_id_w, OT* out, int64_t num_rows, int64_t nnz,
     int64_t vocab, int width, bool mean, int64_t* long_rows,
     int32_t* long_count, int64_t* work_items, int32_t* n_work,
@@ -938,7 +1067,7 @@ static void launch_csr_lookup_forward_q8_t(
   constexpr bool kFloatOut = std::is_same<OT, float>::value;
   const dim3 block(256);
   reset_long_lists(long_count, n_work, stream);
-  const RowTiling t = row_tiling<0, 4>(width, num_rows);
+  const RowTiling t = row_tiling<0, VEC>(width, num_rows);
   const dim3 grid(pick_grid(t.row_waves, block.x / WAVE));
   const int64_t long_thresh =
       forward_long_threshold(t.row_waves, nnz, num_rows, kFloatOut);
@@ -946,12 +1075,12 @@ static void launch_csr_lookup_forward_q8_t(
     dispatch_bool(per_id_w != nullptr, [&](auto has_w_t) {
       constexpr bool MEAN = decltype(mean_t)::value;
       constexpr bool HAS_W = decltype(has_w_t)::value;
-      hipLaunchKernelGGL((csr_fwd_wide<4, MEAN, HAS_W, q8_t, OT>), grid, block,
+      hipLaunchKernelGGL((csr_fwd_wide<VEC, MEAN, HAS_W, QT, OT>), grid, block,
                          0, stream, params, values, splits, per_id_w, out,
                          num_rows, vocab, width, long_thresh, long_rows,
                          long_count, t.tile_w);
       if constexpr (kFloatOut)
-        launch_forward_long_pass<0, 4, MEAN, HAS_W>(
+        launch_forward_long_pass<0, VEC, MEAN, HAS_W>(
             params, values, splits, per_id_w, (float*)out, vocab, width,
             long_rows, long_count, work_items, n_work, t.tile_w, stream);
     });
@@ -967,10 +1096,24 @@ void launch_csr_lookup_forward_q8(const void* packed, const int64_t* values,
                                   int32_t* n_work, hipStream_t stream) {
   dispatch_bool(out_bf16, [&](auto o_bf16) {
     using OT = storage_t<decltype(o_bf16)>;
-    launch_csr_lookup_forward_q8_t((const q8_t*)packed, values, splits,
-                                   per_id_w, (OT*)out, num_rows, nnz, vocab,
-                                   width, mean, long_rows, long_count,
-                                   work_items, n_work, stream);
+    launch_csr_lookup_forward_packed_t<4>(
+        (const q8_t*)packed, values, splits, per_id_w, (OT*)out, num_rows, nnz,
+        vocab, width, mean, long_rows, long_count, work_items, n_work, stream);
+  });
+}
+
+void launch_csr_lookup_forward_q4(const void* packed, const int64_t* values,
+                                  const int64_t* splits, const float* per_id_w,
+                                  void* out, bool out_bf16, int64_t num_rows,
+                                  int64_t nnz, int64_t vocab, int width,
+                                  bool mean, int64_t* long_rows,
+                                  int32_t* long_count, int64_t* work_items,
+                                  int32_t* n_work, hipStream_t stream) {
+  dispatch_bool(out_bf16, [&](auto o_bf16) {
+    using OT = storage_t<decltype(o_bf16)>;
+    launch_csr_lookup_forward_packed_t<8>(
+        (const q4_t*)packed, values, splits, per_id_w, (OT*)out, num_rows, nnz,
+        vocab, width, mean, long_rows, long_count, work_items, n_work, stream);
   });
 }
 
@@ -1089,6 +1232,122 @@ void launch_dequantize_rows_q8(const void* packed, float* out, int64_t n,
   const dim3 grid(pick_grid(t.row_waves, block.x / WAVE));
   hipLaunchKernelGGL(dequantize_rows_kernel, grid, block, 0, stream,
                      (const q8_t*)packed, out, n, width, t.tile_w);
+}
+
+// quantize_rows_q4: in [n, width] fp32 or bf16 -> packed [n, width / 2 + 4],
+// the bytes of FBGEMM's fused 4-bit row-wise quantizer.  The int8 kernel's
+// shape with eight columns per lane and trip and one dword of nibbles stored:
+//   b = fp16(min) (nearest-even), range = max - b,
+//   s = fp16(range == 0 ? 1 : range / 15), and s = 1 if s == 0 or 1/s == inf,
+//   q = clamp(rint((x - b) * (1 / s)), 0, 15)
+// with b and s widened back to fp32 before use.  A constant row of an
+// fp16-representable value stores q = 0, scale 1 and that value; any other
+// constant has range = x - fp16(x) != 0 and takes the general path.  Rows
+// with |x| > 65504 or NaN are outside the contract (fp16 overflows), as they
+// are for FBGEMM.
+template <typename ST>
+__global__ void quantize_rows_q4_kernel(const ST* __restrict__ in,
+                                        unsigned char* __restrict__ out,
+                                        int64_t n, int width, int tile_w) {
+  const WaveCoord wc = wave_coord();
+  const TileCoord tc = tile_coord(wc.lane, tile_w);
+  for (int64_t base = wc.wave_id * tc.rpw; base < n;
+       base += wc.n_waves * tc.rpw) {
+    const int64_t row = base + tc.sub;
+    const bool live = row < n;
+    const ST* src = in + (live ? row : 0) * (int64_t)width;
+    float lo = INFINITY, hi = -INFINITY;
+    if (live) {
+      for (int col0 = tc.tl * 8; col0 < width; col0 += tile_w * 8) {
+        float x[8];
+        pt_load4(src + col0, x);
+        pt_load4(src + col0 + 4, x + 4);
+#pragma unroll
+        for (int v = 0; v < 8; ++v) {
+          lo = fminf(lo, x[v]);
+          hi = fmaxf(hi, x[v]);
+        }
+      }
+    }
+    lo = tile_min(lo, tile_w);
+    hi = tile_max(hi, tile_w);
+    if (!live) continue;
+    const _Float16 bias_h = (_Float16)lo;
+    const float bias = (float)bias_h;
+    const float range = hi - bias;
+    _Float16 scale_h = (_Float16)(range == 0.f ? 1.f : range / 15.f);
+    float scale = (float)scale_h;
+    if (scale == 0.f || isinf(1.f / scale)) {
+      scale_h = (_Float16)1.f;
+      scale = 1.f;
+    }
+    const float inv = 1.f / scale;
+    unsigned char* dst = out + row * (int64_t)(width / 2 + Q4_TAIL);
+    for (int col0 = tc.tl * 8; col0 < width; col0 += tile_w * 8) {
+      float x[8];
+      pt_load4(src + col0, x);
+      pt_load4(src + col0 + 4, x + 4);
+      unsigned int q = 0;
+#pragma unroll
+      for (int v = 0; v < 8; ++v) {
+        const float r = fminf(fmaxf(rintf((x[v] - bias) * inv), 0.f), 15.f);
+        q |= (unsigned int)r << (4 * v);
+      }
+      *reinterpret_cast<unsigned int*>(dst + col0 / 2) = q;
+    }
+    if (tc.tl == 0)
+      *reinterpret_cast<unsigned int*>(dst + width / 2) =
+          (unsigned int)__builtin_bit_cast(unsigned short, scale_h) |
+          ((unsigned int)__builtin_bit_cast(unsigned short, bias_h) << 16);
+  }
+}
+
+// dequantize_rows_q4: packed [n, width / 2 + 4] -> fp32 [n, width] as
+// fma(scale, q, bias), scale and bias widened from fp16.
+__global__ void dequantize_rows_q4_kernel(const q4_t* __restrict__ in,
+                                          float* __restrict__ out, int64_t n,
+                                          int width, int tile_w) {
+  const WaveCoord wc = wave_coord();
+  const TileCoord tc = tile_coord(wc.lane, tile_w);
+  for (int64_t base = wc.wave_id * tc.rpw; base < n;
+       base += wc.n_waves * tc.rpw) {
+    const int64_t row = base + tc.sub;
+    if (row >= n) continue;
+    const unsigned char* src = q4_row(in, row, width);
+    const unsigned int tail = q4_tail(src, width);
+    const float scale = q4_scale(tail), bias = q4_bias(tail);
+    for (int col0 = tc.tl * 8; col0 < width; col0 += tile_w * 8) {
+      float x[8];
+      q4_unpack8(q4_load8(src, col0), x);
+#pragma unroll
+      for (int v = 0; v < 8; ++v) x[v] = fmaf(scale, x[v], bias);
+      pt_store8(out + row * (int64_t)width + col0, x);
+    }
+  }
+}
+
+void launch_quantize_rows_q4(const void* in, bool in_bf16, void* packed,
+                             int64_t n, int width, hipStream_t stream) {
+  if (n <= 0) return;
+  const dim3 block(256);
+  const RowTiling t = row_tiling<0, 8>(width, n);
+  const dim3 grid(pick_grid(t.row_waves, block.x / WAVE));
+  dispatch_bool(in_bf16, [&](auto i_bf16) {
+    using ST = storage_t<decltype(i_bf16)>;
+    hipLaunchKernelGGL((quantize_rows_q4_kernel<ST>), grid, block, 0, stream,
+                       (const ST*)in, (unsigned char*)packed, n, width,
+                       t.tile_w);
+  });
+}
+
+void launch_dequantize_rows_q4(const void* packed, float* out, int64_t n,
+                               int width, hipStream_t stream) {
+  if (n <= 0) return;
+  const dim3 block(256);
+  const RowTiling t = row_tiling<0, 8>(width, n);
+  const dim3 grid(pick_grid(t.row_waves, block.x / WAVE));
+  hipLaunchKernelGGL(dequantize_rows_q4_kernel, grid, block, 0, stream,
+                     (const q4_t*)packed, out, n, width, t.tile_w);
 }
 
 // ---------------------------------------------------------------------------

@@ -32,6 +32,24 @@ void launch_quantize_rows_q8(const void* in, bool in_bf16, void* packed,
 void launch_dequantize_rows_q8(const void* packed, float* out, int64_t n,
                                int width, hipStream_t stream);
 
+// int4 row-wise quantized tables.  packed is [vocab, width / 2 + 4] bytes: per
+// row width / 2 bytes of nibbles (column 2j low, 2j + 1 high), fp16 scale,
+// fp16 bias; the row stands for scale * q + bias.  width % 8 == 0, and the
+// forward needs vocab > 0.
+void launch_csr_lookup_forward_q4(const void* packed, const int64_t* values,
+                                  const int64_t* splits, const float* per_id_w,
+                                  void* out, bool out_bf16, int64_t num_rows,
+                                  int64_t nnz, int64_t vocab, int width,
+                                  bool mean, int64_t* long_rows,
+                                  int32_t* long_count, int64_t* work_items,
+                                  int32_t* n_work, hipStream_t stream);
+// in: [n, width] fp32 or bf16, aligned to four elements; packed:
+// [n, width / 2 + 4].
+void launch_quantize_rows_q4(const void* in, bool in_bf16, void* packed,
+                             int64_t n, int width, hipStream_t stream);
+void launch_dequantize_rows_q4(const void* packed, float* out, int64_t n,
+                               int width, hipStream_t stream);
+
 void launch_row_to_split(const int64_t* rows, int64_t nnz, int64_t num_rows,
                          int64_t* splits, hipStream_t stream);
 

@@ -18,7 +18,10 @@ from torch import nn
 from ..ops.embedding_lookup import (Ragged, _csr_lookup_q8,
                                     check_per_id_weights,
                                     check_betas, csr_lookup_fused_optimizer,
+                                    _check_bits, _check_packed,
+                                    dequantize_rowwise_int4,
                                     dequantize_rowwise_int8, embedding_lookup,
+                                    quantize_rowwise_int4,
                                     quantize_rowwise_int8,
                                     quantized_embedding_lookup, to_int64)
 
@@ -65,7 +68,9 @@ class Embedding(nn.Module):
     output_dim + 8]`` uint8, see ``quantize_rowwise_int8``);
     :meth:`from_quantized` builds such a layer from packed bytes.  A quantized
     layer serves every input kind, forward only: its outputs never require
-    grad and it takes no optimizer.
+    grad and it takes no optimizer.  ``bits=4`` on either selects int4
+    row-wise storage instead (``[input_dim, output_dim / 2 + 4]`` uint8, see
+    ``quantize_rowwise_int4``; ``output_dim`` a multiple of 8).
     """
 
     def __init__(
@@ -98,54 +103,67 @@ class Embedding(nn.Module):
         # (dist_model_parallel.py:889-904).
         self._oob_zero = False
         self.quantized = False
+        self.quantized_bits = None      # 8 or 4 once quantized
 
     def extra_repr(self) -> str:
         s = f"input_dim={self.input_dim}, output_dim={self.output_dim}, combiner={self.combiner}"
-        return s + ", quantized=int8" if self.quantized else s
+        return (s + f", quantized=int{self.quantized_bits}" if self.quantized
+                else s)
 
-    # ------------------------------------------------- int8 row-wise serving
+    # -------------------------------------------- int8 / int4 row-wise serving
 
-    def quantize_(self, chunk_rows: int = 1 << 20):
-        """Converts the table in place to int8 row-wise storage: registers
-        the buffer ``qweight``, removes the ``weight`` parameter (its memory
-        is released) and returns ``self``.  The table stays on its device —
-        a CPU-offloaded table stays on the CPU.  One-way: load the weights
-        first, then quantize, then serve."""
+    def quantize_(self, chunk_rows: int = 1 << 20, bits: int = 8):
+        """Converts the table in place to int8 (``bits=8``) or int4
+        (``bits=4``) row-wise storage: registers the buffer ``qweight``,
+        removes the ``weight`` parameter (its memory is released) and returns
+        ``self``.  The table stays on its device — a CPU-offloaded table
+        stays on the CPU.  One-way: load the weights first, then quantize,
+        then serve; a second call with the same ``bits`` does nothing, one
+        with different ``bits`` raises."""
+        _check_bits(bits)
         if self.quantized:
+            if bits != self.quantized_bits:
+                raise RuntimeError(
+                    f"the table is already quantized to "
+                    f"int{self.quantized_bits}: it cannot be converted to "
+                    f"int{bits}")
             return self
         if getattr(self, "_fused_lr", None) is not None:
             raise RuntimeError("a layer with a fused optimizer enabled "
                                "cannot be quantized: it is being trained")
-        packed = quantize_rowwise_int8(self.weight.detach(), chunk_rows)
+        quantize = quantize_rowwise_int4 if bits == 4 else quantize_rowwise_int8
+        packed = quantize(self.weight.detach(), chunk_rows)
         # a model-parallel shard stays shard-local
         packed.de_local = getattr(self.weight, "de_local", False)
         del self._parameters["weight"]
         self.register_buffer("qweight", packed)
         self.quantized = True
+        self.quantized_bits = bits
         return self
 
     @classmethod
     def from_quantized(cls, packed: torch.Tensor,
-                       combiner: Optional[str] = None) -> "Embedding":
+                       combiner: Optional[str] = None,
+                       bits: int = 8) -> "Embedding":
         """A quantized layer around int8 row-wise ``packed`` bytes
-        (``[input_dim, output_dim + 8]`` uint8); no fp32 table is ever
-        allocated."""
+        (``[input_dim, output_dim + 8]`` uint8) or, with ``bits=4``, int4
+        row-wise ones (``[input_dim, output_dim / 2 + 4]`` uint8); no fp32
+        table is ever allocated."""
         if combiner not in (None, "sum", "mean"):
             raise ValueError(f"invalid combiner {combiner!r}")
-        if (not isinstance(packed, torch.Tensor) or packed.dtype != torch.uint8
-                or packed.dim() != 2 or packed.shape[0] <= 0
-                or packed.shape[1] < 12 or (packed.shape[1] - 8) % 4 != 0):
-            raise ValueError("packed must be uint8 [input_dim, output_dim + 8] "
-                             "with output_dim a positive multiple of 4")
+        width = _check_packed(packed, bits)
+        if packed.shape[0] <= 0:
+            raise ValueError("packed must have at least one row")
         self = cls.__new__(cls)
         nn.Module.__init__(self)
         self.input_dim = int(packed.shape[0])
-        self.output_dim = int(packed.shape[1]) - 8
+        self.output_dim = width
         self.combiner = combiner
         self.sparse_grad = True
         self._oob_zero = False
         self.register_buffer("qweight", packed.detach().contiguous())
         self.quantized = True
+        self.quantized_bits = bits
         return self
 
     def dequantized_weight(self) -> torch.Tensor:
@@ -153,14 +171,18 @@ class Embedding(nn.Module):
         stands for."""
         if not self.quantized:
             raise RuntimeError("dequantized_weight() needs a quantized layer")
+        if self.quantized_bits == 4:
+            return dequantize_rowwise_int4(self.qweight)
         return dequantize_rowwise_int8(self.qweight)
 
     def _quantized_forward(self, ids, per_sample_weights):
         if isinstance(ids, Ragged) or ids.layout == torch.sparse_coo:
             return quantized_embedding_lookup(self.qweight, ids, self.combiner,
-                                              per_sample_weights)
+                                              per_sample_weights,
+                                              bits=self.quantized_bits)
         if self.combiner is None:
-            return quantized_embedding_lookup(self.qweight, ids)
+            return quantized_embedding_lookup(self.qweight, ids,
+                                              bits=self.quantized_bits)
         if ids.dim() < 2:
             raise ValueError("ids with a combiner must have a hotness dimension "
                              "(parity: reference embedding.py:133-135)")
@@ -173,7 +195,7 @@ class Embedding(nn.Module):
         out = quantized_embedding_lookup(
             self.qweight, ids.reshape(-1, h), self.combiner,
             None if per_sample_weights is None
-            else per_sample_weights.reshape(-1, h))
+            else per_sample_weights.reshape(-1, h), bits=self.quantized_bits)
         return out.view(*ids.shape[:-1], self.output_dim)
 
     def _apply(self, fn, recurse=True):
@@ -229,8 +251,8 @@ class Embedding(nn.Module):
             raise ValueError(f"unknown fused optimizer {method!r}")
         check_betas(betas)
         if self.quantized:
-            raise RuntimeError("a quantized (int8) table is inference-only: "
-                               "it takes no optimizer")
+            raise RuntimeError(f"a quantized (int{self.quantized_bits}) table "
+                               "is inference-only: it takes no optimizer")
         if stochastic_rounding and self.weight.dtype != torch.bfloat16:
             raise ValueError("stochastic_rounding needs a bf16 table: an "
                              f"{self.weight.dtype} table has nothing to round")
@@ -282,8 +304,8 @@ class Embedding(nn.Module):
 
     def set_fused_lr(self, lr: float):
         if self.quantized:
-            raise RuntimeError("a quantized (int8) table is inference-only: "
-                               "it takes no optimizer")
+            raise RuntimeError(f"a quantized (int{self.quantized_bits}) table "
+                               "is inference-only: it takes no optimizer")
         if getattr(self, "_fused_lr", None) is None:
             raise RuntimeError("enable_fused_sgd() first")
         with torch.no_grad():
@@ -304,7 +326,8 @@ class Embedding(nn.Module):
         if self.quantized:
             with torch.no_grad():
                 return _csr_lookup_q8(self.qweight, values, row_splits,
-                                      combiner, out_dtype, per_id_w)
+                                      combiner, out_dtype, per_id_w,
+                                      self.quantized_bits)
         if getattr(self, "_fused_lr", None) is not None and self.training:
             adam = None
             if self._fused_method == "lazy_adam":

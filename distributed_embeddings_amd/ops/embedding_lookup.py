@@ -675,13 +675,45 @@ def embedding_lookup(
 # embedding_bag_byte_prepack.  width % 4 == 0 keeps every dword, scale and
 # bias 4-byte aligned.
 
+#
+# int4 row-wise quantized tables
+#
+# Storage: uint8 [vocab, width / 2 + 4], contiguous.  Row i holds width / 2
+# bytes of nibbles q[i, c] in 0..15 (column 2j in the low nibble of byte j,
+# column 2j + 1 in the high one), then fp16 scale[i], then fp16 bias[i], and
+# stands for scale[i] * q[i, c] + bias[i] — byte for byte the "fused 4-bit
+# rowwise" layout of FBGEMM / torch.ops.quantized.embedding_bag_4bit_prepack.
+# That layout only needs an even width; this project requires width % 8 == 0,
+# which makes a lane's dword eight whole columns and keeps the row stride and
+# the scale/bias dword 4-byte aligned.
+#
+# A packed shape alone does not say which of the two formats it holds, so
+# every consumer takes ``bits`` (8 or 4) explicitly.
+
 _Q8_TAIL = 8
+_Q4_TAIL = 4
 
 
-def _check_packed(packed: torch.Tensor) -> int:
-    """Validates an int8 row-wise packed table and returns its width."""
+def _check_bits(bits) -> int:
+    if bits not in (4, 8):
+        raise ValueError(f"bits must be 4 or 8, got {bits!r}")
+    return int(bits)
+
+
+def _check_packed(packed: torch.Tensor, bits: int = 8) -> int:
+    """Validates an int8 (``bits=8``) or int4 (``bits=4``) row-wise packed
+    table and returns its width."""
+    _check_bits(bits)
     if not isinstance(packed, torch.Tensor) or packed.dtype != torch.uint8:
         raise ValueError("a quantized table must be a uint8 tensor")
+    if bits == 4:
+        if (packed.dim() != 2 or packed.shape[1] < _Q4_TAIL + 4
+                or (packed.shape[1] - _Q4_TAIL) % 4 != 0):
+            raise ValueError(
+                f"an int4 quantized table must be [vocab, width / 2 + 4] "
+                f"with width a positive multiple of 8, got "
+                f"{tuple(packed.shape)}")
+        return 2 * (packed.shape[1] - _Q4_TAIL)
     if (packed.dim() != 2 or packed.shape[1] < _Q8_TAIL + 4
             or (packed.shape[1] - _Q8_TAIL) % 4 != 0):
         raise ValueError(
@@ -724,14 +756,10 @@ def quantize_rowwise_int8(weight: torch.Tensor,
         raise ValueError(f"weight must be 2-D, got {weight.dim()}-D")
     if weight.dtype not in (torch.float32, torch.bfloat16):
         raise ValueError("weight must be fp32 or bf16")
-    n, width = weight.shape
+    width = weight.shape[1]
     if width < 4 or width % 4 != 0:
         raise ValueError(f"int8 row-wise quantization needs a width that is "
                          f"a multiple of 4, got width {width}")
-    if chunk_rows is not None and chunk_rows <= 0:
-        raise ValueError("chunk_rows must be positive")
-    weight = weight.detach()
-    step = n if chunk_rows is None else int(chunk_rows)
 
     def convert(rows):
         rows = rows.contiguous()
@@ -739,13 +767,104 @@ def quantize_rowwise_int8(weight: torch.Tensor,
             return _backend.ops().quantize_rows_q8(rows)
         return _quantize_rows_ref(rows.float())
 
+    return _quantize_chunked(weight, chunk_rows, width + _Q8_TAIL, convert)
+
+
+def _quantize_chunked(weight, chunk_rows, row_bytes, convert):
+    """``convert`` over ``chunk_rows`` rows at a time (all by default) into
+    one ``[vocab, row_bytes]`` uint8 table on ``weight``'s device."""
+    if chunk_rows is not None and chunk_rows <= 0:
+        raise ValueError("chunk_rows must be positive")
+    weight = weight.detach()
+    n = weight.shape[0]
+    step = n if chunk_rows is None else int(chunk_rows)
     if step >= n:
         return convert(weight)
-    out = torch.empty(n, width + _Q8_TAIL, dtype=torch.uint8,
-                      device=weight.device)
+    out = torch.empty(n, row_bytes, dtype=torch.uint8, device=weight.device)
     for s in range(0, n, step):
         out[s:s + step].copy_(convert(weight[s:s + step]))
     return out
+
+
+def _quantize_rows_q4_ref(x: torch.Tensor) -> torch.Tensor:
+    """Pure-torch int4 quantizer of fp32 [n, width] rows (CPU path): the
+    contract of :func:`quantize_rowwise_int4`, step by step."""
+    n, width = x.shape
+    out = torch.empty(n, width // 2 + _Q4_TAIL, dtype=torch.uint8,
+                      device=x.device)
+    if n == 0:
+        return out
+    bias_h = x.min(dim=1, keepdim=True).values.to(torch.float16)
+    bias = bias_h.float()
+    rng = x.max(dim=1, keepdim=True).values - bias
+    one = torch.ones_like(rng)
+    scale_h = torch.where(rng == 0, one, rng / 15).to(torch.float16)
+    scale = scale_h.float()
+    unusable = (scale == 0) | torch.isinf(1 / scale)
+    scale_h = torch.where(unusable, one.to(torch.float16), scale_h)
+    inv = 1 / scale_h.float()
+    q = torch.round((x - bias) * inv).clamp_(0, 15).to(torch.uint8)
+    out[:, :width // 2] = q[:, 0::2] | (q[:, 1::2] << 4)
+    tail = torch.cat([scale_h, bias_h], dim=1).contiguous()
+    out[:, width // 2:] = tail.view(torch.uint8)
+    return out
+
+
+def quantize_rowwise_int4(weight: torch.Tensor,
+                          chunk_rows: Optional[int] = None) -> torch.Tensor:
+    """fp32 or bf16 ``[vocab, width]`` -> int4 row-wise packed
+    ``[vocab, width / 2 + 4]`` uint8 on the same device: the bytes of
+    ``torch.ops.quantized.embedding_bag_4bit_prepack`` (of ``weight.float()``
+    for a bf16 table).
+
+    Per row, in fp32: ``b = fp16(min)`` (nearest-even, widened again),
+    ``range = max - b``, ``s = fp16(1 if range == 0 else range / 15)``
+    widened again, ``s = 1`` if ``s == 0`` or ``1 / s`` is infinite, and
+    ``q = clamp(rint((x - b) * (1 / s)), 0, 15)``.  A constant row whose
+    value is fp16-representable stores all-zero nibbles, scale 1 and that
+    value.  Any other constant ``x`` leaves ``range = x - fp16(x) != 0`` and
+    takes the general path, as in torch: nibbles of 15 and a tiny scale,
+    which is negative when ``fp16(x) > x``.  Rows holding ``|x| > 65504`` or NaN are
+    outside the contract, as they are in torch (fp16 overflows); they are
+    not checked for, which would cost a host sync.
+
+    ``width`` must be a multiple of 8 (torch's layout itself only needs an
+    even width).  ``chunk_rows`` as in :func:`quantize_rowwise_int8`.
+    """
+    if weight.dim() != 2:
+        raise ValueError(f"weight must be 2-D, got {weight.dim()}-D")
+    if weight.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError("weight must be fp32 or bf16")
+    width = weight.shape[1]
+    if width < 8 or width % 8 != 0:
+        raise ValueError(
+            f"int4 row-wise quantization needs a width that is a multiple "
+            f"of 8 (the 4-bit layout itself only needs an even width), got "
+            f"width {width}")
+
+    def convert(rows):
+        rows = rows.contiguous()
+        if rows.is_cuda:
+            return _backend.ops().quantize_rows_q4(rows)
+        return _quantize_rows_q4_ref(rows.float())
+
+    return _quantize_chunked(weight, chunk_rows, width // 2 + _Q4_TAIL,
+                             convert)
+
+
+def dequantize_rowwise_int4(packed: torch.Tensor) -> torch.Tensor:
+    """int4 row-wise packed ``[vocab, width / 2 + 4]`` -> fp32
+    ``[vocab, width]``: ``fma(scale, q, bias)`` with scale and bias widened
+    from fp16, one fp32 rounding per element (the CPU path evaluates in fp64,
+    where product and sum are exact, and rounds once)."""
+    width = _check_packed(packed, 4)
+    packed = packed.contiguous()
+    if packed.is_cuda:
+        return _backend.ops().dequantize_rows_q4(packed)
+    nib = packed[:, :width // 2]
+    q = torch.stack([nib & 0xF, nib >> 4], dim=2).reshape(-1, width).double()
+    tail = packed[:, width // 2:].contiguous().view(torch.float16).double()
+    return (q * tail[:, 0:1] + tail[:, 1:2]).float()
 
 
 def dequantize_rowwise_int8(packed: torch.Tensor) -> torch.Tensor:
@@ -764,21 +883,26 @@ def dequantize_rowwise_int8(packed: torch.Tensor) -> torch.Tensor:
 
 
 def _csr_lookup_q8(packed, values, row_splits, combiner, out_dtype=None,
-                   per_id_w=None):
-    """CSR lookup from a packed table: HIP kernel, or on the CPU
-    ``_csr_lookup_ref`` over the gathered, dequantized rows."""
+                   per_id_w=None, bits=8):
+    """CSR lookup from a packed table (int8, or int4 with ``bits=4``): HIP
+    kernel, or on the CPU ``_csr_lookup_ref`` over the gathered, dequantized
+    rows."""
     w32 = _kernel_weights(per_id_w)
     if packed.is_cuda:
-        return _backend.ops().csr_lookup_forward_q8(
-            packed, values, row_splits, combiner == "mean",
-            out_dtype == torch.bfloat16, w32)
+        ext = _backend.ops()
+        forward = (ext.csr_lookup_forward_q4 if bits == 4
+                   else ext.csr_lookup_forward_q8)
+        return forward(packed, values, row_splits, combiner == "mean",
+                       out_dtype == torch.bfloat16, w32)
     vocab = packed.shape[0]
     valid = (values >= 0) & (values < vocab)
     # dequantize only the rows the batch touches, and append one zero row:
     # an out-of-range id becomes that row's id, so the gathered table is
     # never empty, even when no id of the call is valid
     pos = torch.cumsum(valid.to(torch.long), 0) - 1
-    rows = dequantize_rowwise_int8(packed.index_select(0, values[valid]))
+    dequantize = (dequantize_rowwise_int4 if bits == 4
+                  else dequantize_rowwise_int8)
+    rows = dequantize(packed.index_select(0, values[valid]))
     n_valid = rows.shape[0]
     rows = torch.cat([rows, rows.new_zeros(1, rows.shape[1])])
     local = torch.where(valid, pos, torch.full_like(pos, n_valid))
@@ -792,9 +916,13 @@ def quantized_embedding_lookup(
     combiner: Optional[str] = None,
     per_sample_weights: Optional[torch.Tensor] = None,
     out_dtype: Optional[torch.dtype] = None,
+    bits: int = 8,
 ) -> torch.Tensor:
     """:func:`embedding_lookup` from an int8 row-wise quantized table
-    (:func:`quantize_rowwise_int8`), forward only.
+    (:func:`quantize_rowwise_int8`) or, with ``bits=4``, an int4 one
+    (:func:`quantize_rowwise_int4`), forward only.  ``bits`` is explicit
+    because a packed shape alone does not say which format it holds; anything
+    but 4 or 8 raises ``ValueError``.
 
     Same routing: dense ids of any rank without a combiner (a hotness-1
     ``sum``), dense ``[batch, hotness]``, ``Ragged`` (with or without
@@ -807,7 +935,7 @@ def quantized_embedding_lookup(
         raise ValueError(f"combiner must be None, 'sum' or 'mean', got {combiner!r}")
     if out_dtype not in (None, torch.float32, torch.bfloat16):
         raise ValueError("out_dtype must be None, float32 or bfloat16")
-    width = _check_packed(packed)
+    width = _check_packed(packed, bits)
 
     def run(values, splits, comb, w=None):
         if w is not None:
@@ -816,7 +944,7 @@ def quantized_embedding_lookup(
         with torch.no_grad():
             return _csr_lookup_q8(packed, values.long().contiguous(),
                                   splits.long().contiguous(), comb, out_dtype,
-                                  w)
+                                  w, bits)
 
     if isinstance(ids, Ragged):
         if ids.weights is not None and per_sample_weights is not None:

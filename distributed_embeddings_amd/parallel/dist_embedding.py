@@ -100,7 +100,8 @@ def _layer_weight(obj, rows, cols):
 def _offloaded_lookup(layer, ragged, combiner):
     """Lookup from a CPU-offloaded table, quantized or not."""
     if layer.quantized:
-        return quantized_embedding_lookup(layer.qweight, ragged, combiner)
+        return quantized_embedding_lookup(layer.qweight, ragged, combiner,
+                                          bits=layer.quantized_bits)
     return embedding_lookup(layer.weight, ragged, combiner)
 
 
@@ -295,8 +296,9 @@ class DistributedEmbedding(nn.Module):
                                        lyr_seed, betas)
         return self
 
-    def quantize_(self, chunk_rows: int = 1 << 20):
-        """Converts every local table to int8 row-wise storage for serving
+    def quantize_(self, chunk_rows: int = 1 << 20, bits: int = 8):
+        """Converts every local table to int8 (``bits=8``) or int4
+        (``bits=4``) row-wise storage for serving
         (``Embedding.quantize_``): data-parallel tables, fused column-slice
         groups, row shards and CPU-offloaded tables, each on its device.
         Order of use: load the weights, quantize, serve.  Afterwards
@@ -306,7 +308,10 @@ class DistributedEmbedding(nn.Module):
 
         Each local table is quantized by itself, so a column-sliced table
         gets one scale and bias per row *per slice*: slightly more accurate
-        than quantizing the whole row, but not the same bytes."""
+        than quantizing the whole row, but not the same bytes.  int4 needs
+        every local table width, slices included, to be a multiple of 8."""
+        if bits not in (4, 8):
+            raise ValueError(f"bits must be 4 or 8, got {bits!r}")
         layers = (list(self.dp_layers) + list(self.col_layers)
                   + list(self.row_layers))
         # all or nothing: refuse before the first table is converted
@@ -314,15 +319,27 @@ class DistributedEmbedding(nn.Module):
                and not lyr.quantized for lyr in layers):
             raise RuntimeError("tables with a fused optimizer enabled cannot "
                                "be quantized: they are being trained")
+        if any(lyr.quantized and lyr.quantized_bits != bits
+               for lyr in layers):
+            raise RuntimeError("some tables are already quantized to another "
+                               f"format than int{bits}")
+        step = 8 if bits == 4 else 4
+        bad = sorted({lyr.output_dim for lyr in layers
+                      if lyr.output_dim % step != 0})
+        if bad:
+            raise ValueError(
+                f"int{bits} row-wise quantization needs every local table "
+                f"width, column slices included, to be a multiple of {step}, "
+                f"got widths {bad}")
         for lyr in layers:
-            lyr.quantize_(chunk_rows)
+            lyr.quantize_(chunk_rows, bits)
         self.quantized = True
         return self
 
     def _check_not_quantized(self, what):
         if self.quantized:
             raise RuntimeError(
-                f"{what} is not available on quantized (int8) tables: load "
+                f"{what} is not available on quantized tables: load "
                 "the weights first, then quantize_(), then serve")
 
     def set_fused_lr(self, lr: float):

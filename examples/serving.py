@@ -3,14 +3,16 @@
 batches under ``torch.inference_mode`` and report p50/p95/p99 latency.
 
 The full Criteo-1TB-class model fits ONE MI355X (96 GB fp32 tables — or
-48 GB with ``--table-dtype bf16``, about 26 GB with ``--table-dtype int8``:
-row-wise quantized after loading), so single-GPU serving needs no sharding;
+48 GB with ``--table-dtype bf16``, about 26 GB with ``--table-dtype int8``
+and about 13 GB with ``--table-dtype int4``: row-wise quantized after
+loading), so single-GPU serving needs no sharding;
 ``--graph`` captures the scoring step in a hipGraph for launch-bound small
 batches.
 
   python examples/serving.py --batch-size 4096 --iters 200 [--graph]
   python examples/serving.py --weights dump.npz        # from dlrm_main --dump-embeddings
   python examples/serving.py --table-dtype int8        # quantize the tables, then score
+  python examples/serving.py --table-dtype int4        # the same with 4-bit rows
 """
 
 import argparse
@@ -36,9 +38,10 @@ def parse_args():
     p.add_argument("--weights", default=None,
                    help="npz from dlrm_main --dump-embeddings, or a "
                         "checkpoint directory (table_*.npy; mmap-loaded)")
-    p.add_argument("--table-dtype", default="fp32", choices=["fp32", "bf16", "int8"],
-                   help="int8: build and load the tables in fp32, quantize "
-                        "them row-wise to int8, then score")
+    p.add_argument("--table-dtype", default="fp32",
+                   choices=["fp32", "bf16", "int8", "int4"],
+                   help="int8 / int4: build and load the tables in fp32, "
+                        "quantize them row-wise, then score")
     p.add_argument("--table-size-cap", type=int, default=None)
     p.add_argument("--graph", action="store_true",
                    help="capture the scoring step in a hipGraph")
@@ -68,13 +71,13 @@ def main():
         else:
             with np.load(args.weights) as z:
                 model.embeddings.set_weights([z[k] for k in z.files])
-    if args.table_dtype == "int8":
+    if args.table_dtype in ("int8", "int4"):
         # order of use: load, then quantize, then serve
         before = table_bytes(model.embeddings)
-        model.embeddings.quantize_()
+        model.embeddings.quantize_(bits=int(args.table_dtype[3:]))
         after = table_bytes(model.embeddings)
         print(f"tables: {before / 2**20:.1f} MiB fp32 -> "
-              f"{after / 2**20:.1f} MiB int8 row-wise "
+              f"{after / 2**20:.1f} MiB {args.table_dtype} row-wise "
               f"({before / after:.2f}x smaller)")
 
     b = args.batch_size
