@@ -10,11 +10,12 @@ Public API (parity: reference ``distributed_embeddings/__init__.py:17-27``):
 """
 
 from .ops.embedding_lookup import (Ragged, dequantize_rowwise_int4,
-                                   dequantize_rowwise_int8, embedding_lookup,
+                                   dequantize_rowwise_int8, deterministic,
+                                   embedding_lookup, is_deterministic,
                                    quantize_rowwise_int4,
                                    quantize_rowwise_int8,
                                    quantized_embedding_lookup, row_to_split,
-                                   stochastic_round_bf16)
+                                   set_deterministic, stochastic_round_bf16)
 from .layers.embedding import ConcatOneHotEmbedding, Embedding, scaled_uniform_init
 from .layers.integer_lookup import IntegerLookup
 from .parallel.strategy import DistEmbeddingStrategy, TableConfig
@@ -43,6 +44,9 @@ __all__ = [
     "dequantize_rowwise_int4",
     "quantized_embedding_lookup",
     "stochastic_round_bf16",
+    "set_deterministic",
+    "is_deterministic",
+    "deterministic",
     "Embedding",
     "IntegerLookup",
     "ConcatOneHotEmbedding",

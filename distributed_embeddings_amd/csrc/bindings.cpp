@@ -110,10 +110,33 @@ const float* per_id_w_ptr(const std::optional<torch::Tensor>& per_id_w,
   return w.data_ptr<float>();
 }
 
+// Deterministic mode's buffers, allocated only when the mode is on and sized
+// from host-known shapes (no sync): the slab holds one fp32 partial row per
+// work item and has the work list's capacity, nnz / 64 + 64 rows -- a long
+// row has len > 128 ids, so its ceil(len / 128) items number fewer than
+// len / 64 -- and work_base one int32 per possible long row.
+struct DetAlloc {
+  torch::Tensor slab, work_base;
+  DetAlloc(bool deterministic, int64_t nnz, int64_t max_long_rows, int width,
+             const torch::TensorOptions& like) {
+    if (!deterministic) return;
+    slab = torch::empty({nnz / 64 + 64, (int64_t)width},
+                        like.dtype(torch::kFloat32));
+    work_base = torch::empty({max_long_rows}, like.dtype(torch::kInt32));
+  }
+  float* slab_ptr() const {
+    return slab.defined() ? slab.data_ptr<float>() : nullptr;
+  }
+  int32_t* work_base_ptr() const {
+    return work_base.defined() ? work_base.data_ptr<int32_t>() : nullptr;
+  }
+};
+
 torch::Tensor csr_lookup_forward(torch::Tensor params, torch::Tensor values,
                                  torch::Tensor row_splits, bool mean,
                                  bool out_bf16,
-                                 std::optional<torch::Tensor> per_id_w) {
+                                 std::optional<torch::Tensor> per_id_w,
+                                 bool deterministic) {
   CHECK_CUDA(params); CHECK_CUDA(values); CHECK_CUDA(row_splits);
   CHECK_CONTIG(params); CHECK_CONTIG(values); CHECK_CONTIG(row_splits);
   TORCH_CHECK(params.dtype() == torch::kFloat32 ||
@@ -128,7 +151,8 @@ torch::Tensor csr_lookup_forward(torch::Tensor params, torch::Tensor values,
   // accumulation is fp32 regardless of table/output storage dtype; bf16 out
   // stores RNE-rounded results directly (no separate cast kernel).  The
   // long-segment split needs fp32 atomics, so bf16-out launches reduce
-  // every row in-register instead (fine for bounded forward hotness).
+  // every row in-register instead (fine for bounded forward hotness);
+  // deterministic mode combines without atomics and splits them too.
   auto out = torch::empty({num_rows, width},
                           params.options().dtype(
                               out_bf16 ? torch::kBFloat16 : torch::kFloat32));
@@ -138,6 +162,8 @@ torch::Tensor csr_lookup_forward(torch::Tensor params, torch::Tensor values,
     auto long_count = torch::empty({1}, values.options().dtype(torch::kInt32));
     auto work_items = torch::empty({nnz_in / 64 + 64}, values.options());
     auto n_work = torch::empty({1}, values.options().dtype(torch::kInt32));
+    const DetAlloc det(deterministic, nnz_in, num_rows, width,
+                         params.options());
     launch_csr_lookup_forward(params.data_ptr(),
                               params.dtype() == torch::kBFloat16,
                               values.data_ptr<int64_t>(),
@@ -147,7 +173,8 @@ torch::Tensor csr_lookup_forward(torch::Tensor params, torch::Tensor values,
                               long_rows.data_ptr<int64_t>(),
                               long_count.data_ptr<int32_t>(),
                               work_items.data_ptr<int64_t>(),
-                              n_work.data_ptr<int32_t>(), current_stream());
+                              n_work.data_ptr<int32_t>(), det.slab_ptr(),
+                              det.work_base_ptr(), current_stream());
   }
   return out;
 }
@@ -185,7 +212,8 @@ torch::Tensor packed_lookup_forward(PackedForwardLauncher launch,
                                     const torch::Tensor& values,
                                     const torch::Tensor& row_splits, bool mean,
                                     bool out_bf16,
-                                    const std::optional<torch::Tensor>& per_id_w) {
+                                    const std::optional<torch::Tensor>& per_id_w,
+                                    bool deterministic) {
   CHECK_CUDA(values); CHECK_CUDA(row_splits);
   CHECK_CONTIG(values); CHECK_CONTIG(row_splits);
   TORCH_CHECK(values.dtype() == torch::kInt64, "values must be int64");
@@ -201,7 +229,8 @@ torch::Tensor packed_lookup_forward(PackedForwardLauncher launch,
   // an empty table has no row to read: every id is out of range
   if (vocab == 0) return torch::zeros({num_rows, width}, opts);
   // fp32 accumulation; bf16 out is stored directly and, as for the fp32 and
-  // bf16 tables, reduces every row in-register (no long-row split)
+  // bf16 tables, reduces every row in-register (no long-row split) unless
+  // the call is deterministic
   auto out = torch::empty({num_rows, width}, opts);
   if (num_rows > 0) {
     const int64_t nnz_in = values.numel();
@@ -209,12 +238,14 @@ torch::Tensor packed_lookup_forward(PackedForwardLauncher launch,
     auto long_count = torch::empty({1}, values.options().dtype(torch::kInt32));
     auto work_items = torch::empty({nnz_in / 64 + 64}, values.options());
     auto n_work = torch::empty({1}, values.options().dtype(torch::kInt32));
+    const DetAlloc det(deterministic, nnz_in, num_rows, width,
+                         packed.options());
     launch(packed.data_ptr(), values.data_ptr<int64_t>(),
            row_splits.data_ptr<int64_t>(), w_ptr, out.data_ptr(), out_bf16,
            num_rows, nnz_in, vocab, width, mean,
            long_rows.data_ptr<int64_t>(), long_count.data_ptr<int32_t>(),
            work_items.data_ptr<int64_t>(), n_work.data_ptr<int32_t>(),
-           current_stream());
+           det.slab_ptr(), det.work_base_ptr(), current_stream());
   }
   return out;
 }
@@ -222,21 +253,24 @@ torch::Tensor packed_lookup_forward(PackedForwardLauncher launch,
 torch::Tensor csr_lookup_forward_q8(torch::Tensor packed, torch::Tensor values,
                                     torch::Tensor row_splits, bool mean,
                                     bool out_bf16,
-                                    std::optional<torch::Tensor> per_id_w) {
+                                    std::optional<torch::Tensor> per_id_w,
+                                    bool deterministic) {
   CHECK_Q8_PACKED(packed);
   return packed_lookup_forward(&launch_csr_lookup_forward_q8, packed,
                                (int)packed.size(1) - 8, values, row_splits,
-                               mean, out_bf16, per_id_w);
+                               mean, out_bf16, per_id_w, deterministic);
 }
 
 torch::Tensor csr_lookup_forward_q4(torch::Tensor packed, torch::Tensor values,
                                     torch::Tensor row_splits, bool mean,
                                     bool out_bf16,
-                                    std::optional<torch::Tensor> per_id_w) {
+                                    std::optional<torch::Tensor> per_id_w,
+                                    bool deterministic) {
   CHECK_Q4_PACKED(packed);
   return packed_lookup_forward(&launch_csr_lookup_forward_q4, packed,
                                2 * ((int)packed.size(1) - 4), values,
-                               row_splits, mean, out_bf16, per_id_w);
+                               row_splits, mean, out_bf16, per_id_w,
+                               deterministic);
 }
 
 torch::Tensor quantize_rows_q8(torch::Tensor weight) {
@@ -401,7 +435,8 @@ std::vector<torch::Tensor> csr_lookup_backward(torch::Tensor grad_out,
                                                torch::Tensor row_splits,
                                                int64_t vocab, bool mean,
                                                std::optional<torch::Tensor>
-                                                   per_id_w) {
+                                                   per_id_w,
+                                               bool deterministic) {
   CHECK_CUDA(grad_out); CHECK_CUDA(values); CHECK_CUDA(row_splits);
   CHECK_CONTIG(grad_out); CHECK_CONTIG(values); CHECK_CONTIG(row_splits);
   TORCH_CHECK(grad_out.dtype() == torch::kFloat32 ||
@@ -436,6 +471,7 @@ std::vector<torch::Tensor> csr_lookup_backward(torch::Tensor grad_out,
     auto long_count = torch::empty({1}, i32);
     auto work_items = torch::empty({nnz / 64 + 64}, i64);
     auto n_work = torch::empty({1}, i32);
+    const DetAlloc det(deterministic, nnz, nu, width, f32);
     launch_csr_lookup_forward(grad_out.data_ptr(),
                               grad_out.dtype() == torch::kBFloat16,
                               ss.srow.data_ptr<int64_t>(),
@@ -445,7 +481,8 @@ std::vector<torch::Tensor> csr_lookup_backward(torch::Tensor grad_out,
                               long_rows.data_ptr<int64_t>(),
                               long_count.data_ptr<int32_t>(),
                               work_items.data_ptr<int64_t>(),
-                              n_work.data_ptr<int32_t>(), stream);
+                              n_work.data_ptr<int32_t>(), det.slab_ptr(),
+                              det.work_base_ptr(), stream);
   }
   return {unique_ids, unique_grad};
 }
@@ -731,15 +768,17 @@ void csr_fused_optimizer_apply(torch::Tensor weight, torch::Tensor state,
                                std::optional<torch::Tensor> per_id_w,
                                std::optional<torch::Tensor> sr,
                                std::optional<torch::Tensor> adam_step,
-                               double beta1, double beta2) {
+                               double beta1, double beta2,
+                               bool deterministic) {
   // adam_step (int64 [1] on the device) selects lazy Adam: state is
   // [2, vocab, width], adagrad has to be false, and an apply that launches
   // adds 1 to the step on the device.
   // All-device sorted pipeline (no host sync; hipGraph-capturable):
   // sort (id, pos) -> permute row-ids -> head-flag unique -> segment pad ->
   // one direct update per unique row (long segments chunked with one atomic
-  // per partial).  Replaces both torch sparse grads and the naive atomic
-  // scatter (hot-row same-address chains).
+  // per partial, or, deterministic, one slab row per partial and a
+  // fixed-order combine).  Replaces both torch sparse grads and the naive
+  // atomic scatter (hot-row same-address chains).
   CHECK_CUDA(weight); CHECK_CUDA(values); CHECK_CUDA(row_splits);
   CHECK_CUDA(grad_out); CHECK_CUDA(lr);
   CHECK_CONTIG(weight); CHECK_CONTIG(values); CHECK_CONTIG(row_splits);
@@ -799,11 +838,13 @@ void csr_fused_optimizer_apply(torch::Tensor weight, torch::Tensor state,
     cfg.step = adam_step->data_ptr<int64_t>();
     cfg.a_t = a_t.data_ptr<float>();
   }
-  if (adagrad || adam || wbf16) {
+  if (adagrad || adam || wbf16 || deterministic) {
     scratch_rows = nnz / (128 + 1) + 1;  // max possible long segments
     scratch = torch::empty({scratch_rows, (int64_t)width}, f32);
     scratch_ptr = scratch.data_ptr<float>();
   }
+  // a long segment has more than 128 ids: at most scratch_rows of them
+  const DetAlloc det(deterministic, nnz, nnz / (128 + 1) + 1, width, f32);
   launch_sorted_optimizer_update(weight.data_ptr(), wbf16, state_ptr,
                                  (float)eps, ss.sorted_ids.data_ptr<int64_t>(),
                                  ss.seg.data_ptr<int64_t>(),
@@ -817,7 +858,8 @@ void csr_fused_optimizer_apply(torch::Tensor weight, torch::Tensor state,
                                  work_items.data_ptr<int64_t>(),
                                  n_work.data_ptr<int32_t>(), scratch_ptr,
                                  scratch_rows, adagrad, rowwise, sr_p,
-                                 adam ? &cfg : nullptr, stream);
+                                 adam ? &cfg : nullptr, det.slab_ptr(),
+                                 det.work_base_ptr(), stream);
 }
 
 // fp32 [n] -> bf16 [n], stochastically rounded with the bits the fused
@@ -1138,13 +1180,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("params"), pybind11::arg("values"),
         pybind11::arg("row_splits"), pybind11::arg("mean"),
         pybind11::arg("out_bf16") = false,
-        pybind11::arg("per_id_w") = pybind11::none());
+        pybind11::arg("per_id_w") = pybind11::none(),
+        pybind11::arg("deterministic") = false);
   m.def("csr_lookup_forward_q8", &csr_lookup_forward_q8,
         "CSR gather-reduce from an int8 row-wise quantized table (gfx950)",
         pybind11::arg("packed"), pybind11::arg("values"),
         pybind11::arg("row_splits"), pybind11::arg("mean"),
         pybind11::arg("out_bf16") = false,
-        pybind11::arg("per_id_w") = pybind11::none());
+        pybind11::arg("per_id_w") = pybind11::none(),
+        pybind11::arg("deterministic") = false);
   m.def("quantize_rows_q8", &quantize_rows_q8,
         "fp32/bf16 [n, width] -> int8 row-wise packed [n, width + 8] (gfx950)",
         pybind11::arg("weight"));
@@ -1156,7 +1200,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("packed"), pybind11::arg("values"),
         pybind11::arg("row_splits"), pybind11::arg("mean"),
         pybind11::arg("out_bf16") = false,
-        pybind11::arg("per_id_w") = pybind11::none());
+        pybind11::arg("per_id_w") = pybind11::none(),
+        pybind11::arg("deterministic") = false);
   m.def("quantize_rows_q4", &quantize_rows_q4,
         "fp32/bf16 [n, width] -> int4 row-wise packed [n, width / 2 + 4] "
         "(gfx950)",
@@ -1168,7 +1213,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "sparse backward: sort + unique + segmented sum (gfx950)",
         pybind11::arg("grad_out"), pybind11::arg("values"),
         pybind11::arg("row_splits"), pybind11::arg("vocab"),
-        pybind11::arg("mean"), pybind11::arg("per_id_w") = pybind11::none());
+        pybind11::arg("mean"), pybind11::arg("per_id_w") = pybind11::none(),
+        pybind11::arg("deterministic") = false);
   m.def("csr_lookup_weight_grad", &csr_lookup_weight_grad,
         "gradient of the per-id weights of a weighted lookup (gfx950)",
         pybind11::arg("grad_out"), pybind11::arg("params"),
@@ -1211,7 +1257,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("per_id_w") = pybind11::none(),
         pybind11::arg("sr") = pybind11::none(),
         pybind11::arg("adam_step") = pybind11::none(),
-        pybind11::arg("beta1") = 0.9, pybind11::arg("beta2") = 0.999);
+        pybind11::arg("beta1") = 0.9, pybind11::arg("beta2") = 0.999,
+        pybind11::arg("deterministic") = false);
   m.def("stochastic_round_bf16", &stochastic_round_bf16,
         "fp32 -> bf16 with the fused optimizers' stochastic rounding (gfx950)",
         pybind11::arg("x"), pybind11::arg("seed"), pybind11::arg("step") = 0,

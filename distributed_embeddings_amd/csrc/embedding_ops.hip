@@ -10,7 +10,10 @@
 //     loads; widths >256 loop over 256-element chunks.  Grid-stride over rows.
 //     Power-law skew: rows longer than an adaptive threshold are pushed to a
 //     device-side list, expanded to exact (row, 128-id chunk) work items, and
-//     reduced by a second kernel with atomic combine (no host sync).
+//     reduced by a second kernel with atomic combine (no host sync).  The
+//     opt-in deterministic mode stores the chunk partials to a slab and adds
+//     them in a fixed order instead: no float atomics in the forward, the
+//     sparse backward or the fused optimizers.
 //   * csr_lookup_forward_q8 / quantize_rows / dequantize_rows — the same
 //     forward from int8 row-wise quantized tables (width bytes + fp32 scale +
 //     fp32 bias per row, inference only): the wide and long kernels above
@@ -774,12 +777,17 @@ __global__ void csr_fwd_wide(const PT* __restrict__ params,
 }
 
 // Builds the exact (long-row, chunk) work list so consumer kernels never
-// probe empty chunk slots.  Item encoding: (li << 24) | chunk.
+// probe empty chunk slots.  Item encoding: (li << 24) | chunk.  Long row li
+// owns the items base .. base + chunks - 1, in chunk order; WITH_BASE
+// (deterministic mode) also records work_base[li] = base.  The base comes
+// from an integer atomic and may differ between runs: it only names slots.
+template <bool WITH_BASE>
 __global__ void expand_long_work(const int64_t* __restrict__ long_rows,
                                  const int32_t* __restrict__ long_count,
                                  const int64_t* __restrict__ splits,
                                  int64_t* __restrict__ work_items,
-                                 int32_t* __restrict__ n_work) {
+                                 int32_t* __restrict__ n_work,
+                                 int32_t* __restrict__ work_base) {
   const WaveCoord wc = wave_coord();
   const int64_t n_long = *long_count;
   for (int64_t li = wc.wave_id; li < n_long; li += wc.n_waves) {
@@ -787,7 +795,10 @@ __global__ void expand_long_work(const int64_t* __restrict__ long_rows,
     const int64_t len = splits[row + 1] - splits[row];
     const int64_t chunks = (len + LONG_T - 1) / LONG_T;
     int base = 0;
-    if (wc.lane == 0) base = atomicAdd(n_work, (int32_t)chunks);
+    if (wc.lane == 0) {
+      base = atomicAdd(n_work, (int32_t)chunks);
+      if constexpr (WITH_BASE) work_base[li] = base;
+    }
     base = __shfl(base, 0);
     for (int64_t c = wc.lane; c < chunks; c += WAVE) {
       work_items[base + c] = (li << 24) | c;
@@ -819,8 +830,11 @@ __device__ __forceinline__ LongChunk long_chunk(
 // (TILE > 0): one wave per item, all 64 lanes active — the 64/TILE sub-tiles
 // each reduce a strided share of the chunk.  Wide (TILE == 0): tile_w lanes
 // per item as in kernel A.  Partials combine with global atomicAdd (out
-// pre-zeroed by A).
-template <int TILE, int VEC, bool MEAN, bool HAS_W, typename PT>
+// pre-zeroed by A).  DET (deterministic mode): `out` is the slab, fp32
+// [n_items_max, width], and item `item` stores the value it would have added
+// to slab row `item` with plain vector stores; long_slab_group_sum and
+// long_slab_combine then add the rows in a fixed order.
+template <int TILE, int VEC, bool MEAN, bool HAS_W, bool DET, typename PT>
 __global__ void csr_fwd_long(const PT* __restrict__ params,
                              const int64_t* __restrict__ values,
                              const int64_t* __restrict__ splits,
@@ -840,21 +854,119 @@ __global__ void csr_fwd_long(const PT* __restrict__ params,
     const LongChunk c = long_chunk(work_items, long_rows, splits, item);
     if (c.ks >= c.e) continue;
     const float inv = (MEAN && c.e > c.s) ? 1.f / (float)(c.e - c.s) : 1.f;
-    float* orow = out + c.row * (int64_t)width;
+    float* orow = out + (DET ? item : c.row) * (int64_t)width;
     if constexpr (TILE > 0) {
       const float acc = narrow_reduce<TILE, WAVE / TILE, 4, HAS_W, true>(
           params, values, per_id_w, vocab, width, c.ks, c.ke, wc.lane);
-      if (wc.lane < TILE && wc.lane < width)
-        atomicAdd(&orow[wc.lane], acc * inv);
+      if (wc.lane < TILE && wc.lane < width) {
+        if constexpr (DET) orow[wc.lane] = acc * inv;
+        else atomicAdd(&orow[wc.lane], acc * inv);
+      }
     } else {
       for (int col0 = tc.tl * VEC; col0 < width; col0 += tile_w * VEC) {
         float acc[VEC];
         wide_accumulate<VEC, HAS_W, true>(params, values, per_id_w, vocab,
                                           width, col0, c.ks, c.ke, acc);
+        if constexpr (DET) {
 #pragma unroll
-        for (int v = 0; v < VEC; ++v) atomicAdd(&orow[col0 + v], acc[v] * inv);
+          for (int v = 0; v < VEC; ++v) acc[v] *= inv;
+          pt_storev<VEC>(orow + col0, acc);
+        } else {
+#pragma unroll
+          for (int v = 0; v < VEC; ++v)
+            atomicAdd(&orow[col0 + v], acc[v] * inv);
+        }
       }
     }
+  }
+}
+
+// ---------------------------------------------------------------------------
+// Deterministic mode: fixed-order combine of the long rows' slab partials.
+//
+// Long row li with chunks = ceil(len / LONG_T) owns the slab rows
+// base .. base + chunks - 1 (base = work_base[li]), row base + c holding the
+// partial p_c of its chunk c.  The row's sum is defined per column as
+//   S_g = ((p_{gG} + p_{gG+1}) + ...) + p_{min(gG+G, chunks)-1}
+//         for each group g of SLAB_G consecutive chunks, left to right,
+//   t   = ((S_0 + S_1) + ...) + S_{ceil(chunks / G) - 1}, left to right,
+// all in fp32.  It is a function of the partials and of `chunks` alone --
+// not of the grid, the wave, li or base -- and for chunks <= SLAB_G it is the
+// plain left-to-right sum.  long_slab_group_sum forms the S_g, one wave per
+// group, in place (S_g replaces p_{gG}; a mega-segment of 13k chunks keeps
+// 200 waves busy); long_slab_combine adds the S_g of one row and stores.
+// Only the adds are ordered: SLAB_FLIGHT loads are in flight ahead of them.
+// ---------------------------------------------------------------------------
+#define SLAB_G 64
+#define SLAB_FLIGHT 8
+
+// p[0] + p[stride] + ... + p[(n - 1) * stride], left to right; n >= 1 and
+// wave-uniform.
+__device__ __forceinline__ float slab_ordered_sum(const float* p,
+                                                  int64_t stride, int64_t n) {
+  float t = p[0];
+  int64_t j = 1;
+  for (; j + SLAB_FLIGHT <= n; j += SLAB_FLIGHT) {
+    float v[SLAB_FLIGHT];
+#pragma unroll
+    for (int u = 0; u < SLAB_FLIGHT; ++u) v[u] = p[(j + u) * stride];
+#pragma unroll
+    for (int u = 0; u < SLAB_FLIGHT; ++u) t = t + v[u];
+  }
+  for (; j < n; ++j) t = t + p[j * stride];
+  return t;
+}
+
+// Level 1: the wave that meets the first item of a group (chunk % SLAB_G ==
+// 0) sums the group's slab rows into that first row.  No other wave reads or
+// writes the group's rows, and a lane touches its own columns only, so the
+// in-place store needs no fence.  Rows of one chunk group of one are left as
+// they are.
+__global__ void long_slab_group_sum(float* slab, int width,
+                                    const int64_t* __restrict__ long_rows,
+                                    const int64_t* __restrict__ splits,
+                                    const int64_t* __restrict__ work_items,
+                                    const int32_t* __restrict__ n_work_ptr) {
+  const WaveCoord wc = wave_coord();
+  const int64_t n_items = *n_work_ptr;
+  for (int64_t item = wc.wave_id; item < n_items; item += wc.n_waves) {
+    const int64_t w = work_items[item];
+    const int64_t chunk = w & 0xffffff;
+    if (chunk % SLAB_G != 0) continue;
+    const int64_t row = long_rows[w >> 24];
+    const int64_t len = splits[row + 1] - splits[row];
+    const int64_t chunks = (len + LONG_T - 1) / LONG_T;
+    const int64_t n = min((int64_t)SLAB_G, chunks - chunk);
+    if (n < 2) continue;
+    float* first = slab + item * (int64_t)width;
+    for (int c = wc.lane; c < width; c += WAVE)
+      first[c] = slab_ordered_sum(first + c, width, n);
+  }
+}
+
+// Level 2: one wave per long row adds the row's group sums in group order and
+// stores the total -- to out[row] (forward and sparse backward; OT fp32, or
+// bf16 rounded to nearest-even), or with TO_SCRATCH to scratch row li, which
+// the fused optimizers' finalize kernels then read.
+template <bool TO_SCRATCH, typename OT>
+__global__ void long_slab_combine(const float* __restrict__ slab,
+                                  OT* __restrict__ dst, int width,
+                                  const int64_t* __restrict__ long_rows,
+                                  const int32_t* __restrict__ long_count,
+                                  const int64_t* __restrict__ splits,
+                                  const int32_t* __restrict__ work_base) {
+  const WaveCoord wc = wave_coord();
+  const int64_t n_long = *long_count;
+  for (int64_t li = wc.wave_id; li < n_long; li += wc.n_waves) {
+    const int64_t row = long_rows[li];
+    const int64_t len = splits[row + 1] - splits[row];
+    const int64_t chunks = (len + LONG_T - 1) / LONG_T;
+    const int64_t groups = (chunks + SLAB_G - 1) / SLAB_G;
+    const float* first = slab + (int64_t)work_base[li] * width;
+    OT* drow = dst + (TO_SCRATCH ? li : row) * (int64_t)width;
+    for (int c = wc.lane; c < width; c += WAVE)
+      pt_store(&drow[c], slab_ordered_sum(first + c, (int64_t)SLAB_G * width,
+                                          groups));
   }
 }
 
@@ -943,9 +1055,10 @@ using storage_t = std::conditional_t<IsBf16::value, bf16_t, float>;
 // Adaptive long threshold of the forward: when there are plenty of rows the
 // chip is full without splitting, so only true outliers (>4x the average and
 // >LONG_T) offload; with few rows split aggressively for parallelism.  bf16
-// out: the long-row combine needs fp32 atomics, so the split is disabled —
+// out: the atomic long-row combine needs fp32, so the split is disabled —
 // every row reduces in-register in kernel A (callers request bf16 out only on
-// bounded-hotness forwards).
+// bounded-hotness forwards).  The deterministic combine stores through
+// pt_store and passes float_out = true for bf16 out as well.
 static int64_t forward_long_threshold(int64_t row_waves, int64_t nnz,
                                       int64_t num_rows, bool float_out) {
   if (!float_out) return INT64_MAX;
@@ -977,11 +1090,59 @@ static void launch_forward_long_pass(const PT* params, const int64_t* values,
                                      int64_t* work_items, int32_t* n_work,
                                      int tile_w, hipStream_t stream) {
   const dim3 block(256);
-  hipLaunchKernelGGL(expand_long_work, dim3(512), block, 0, stream, long_rows,
-                     long_count, splits, work_items, n_work);
-  hipLaunchKernelGGL((csr_fwd_long<TILE, VEC, MEAN, HAS_W, PT>), dim3(2048),
-                     block, 0, stream, params, values, splits, per_id_w, out,
-                     vocab, width, long_rows, work_items, n_work, tile_w);
+  hipLaunchKernelGGL(expand_long_work<false>, dim3(512), block, 0, stream,
+                     long_rows, long_count, splits, work_items, n_work,
+                     (int32_t*)nullptr);
+  hipLaunchKernelGGL((csr_fwd_long<TILE, VEC, MEAN, HAS_W, false, PT>),
+                     dim3(2048), block, 0, stream, params, values, splits,
+                     per_id_w, out, vocab, width, long_rows, work_items, n_work,
+                     tile_w);
+}
+
+// Deterministic mode: where to put the long rows' partials.  slab is fp32
+// [work item capacity, width], work_base int32 [long-row capacity]; a null
+// slab means the mode is off.
+struct DetBuffers {
+  float* slab;
+  int32_t* work_base;
+};
+
+// The fixed-order sum of every long row's slab partials, stored to
+// dst[row] (or, TO_SCRATCH, to scratch row li).
+template <bool TO_SCRATCH, typename OT>
+static void launch_slab_combine(const DetBuffers& det, OT* dst, int width,
+                                const int64_t* long_rows,
+                                const int32_t* long_count,
+                                const int64_t* splits,
+                                const int64_t* work_items,
+                                const int32_t* n_work, hipStream_t stream) {
+  const dim3 block(256);
+  hipLaunchKernelGGL(long_slab_group_sum, dim3(2048), block, 0, stream,
+                     det.slab, width, long_rows, splits, work_items, n_work);
+  hipLaunchKernelGGL((long_slab_combine<TO_SCRATCH, OT>), dim3(256), block, 0,
+                     stream, det.slab, dst, width, long_rows, long_count,
+                     splits, det.work_base);
+}
+
+// The deterministic long pass: the same work list with each row's base
+// recorded, partials into the slab, then the fixed-order combine into out
+// (fp32 or bf16).
+template <int TILE, int VEC, bool MEAN, bool HAS_W, typename PT, typename OT>
+static void launch_forward_long_pass_det(
+    const PT* params, const int64_t* values, const int64_t* splits,
+    const float* per_id_w, OT* out, int64_t vocab, int width,
+    int64_t* long_rows, int32_t* long_count, int64_t* work_items,
+    int32_t* n_work, int tile_w, const DetBuffers& det, hipStream_t stream) {
+  const dim3 block(256);
+  hipLaunchKernelGGL(expand_long_work<true>, dim3(512), block, 0, stream,
+                     long_rows, long_count, splits, work_items, n_work,
+                     det.work_base);
+  hipLaunchKernelGGL((csr_fwd_long<TILE, VEC, MEAN, HAS_W, true, PT>),
+                     dim3(2048), block, 0, stream, params, values, splits,
+                     per_id_w, det.slab, vocab, width, long_rows, work_items,
+                     n_work, tile_w);
+  launch_slab_combine<false>(det, out, width, long_rows, long_count, splits,
+                             work_items, n_work, stream);
 }
 
 template <typename PT, typename OT>
@@ -992,6 +1153,7 @@ static void launch_csr_lookup_forward_t(const PT* params, const int64_t* values,
                                         int64_t vocab, int width, bool mean,
                                         int64_t* long_rows, int32_t* long_count,
                                         int64_t* work_items, int32_t* n_work,
+                                        const DetBuffers& det,
                                         hipStream_t stream) {
   const dim3 block(256);
   reset_long_lists(long_count, n_work, stream);
@@ -1000,8 +1162,8 @@ static void launch_csr_lookup_forward_t(const PT* params, const int64_t* values,
     constexpr bool kFloatOut = std::is_same<OT, float>::value;
     const RowTiling t = row_tiling<TILE, VEC>(width, num_rows);
     const dim3 grid(pick_grid(t.row_waves, block.x / WAVE));
-    const int64_t long_thresh =
-        forward_long_threshold(t.row_waves, nnz, num_rows, kFloatOut);
+    const int64_t long_thresh = forward_long_threshold(
+        t.row_waves, nnz, num_rows, kFloatOut || det.slab != nullptr);
     dispatch_bool(mean, [&](auto mean_t) {
       dispatch_bool(per_id_w != nullptr, [&](auto has_w_t) {
         constexpr bool MEAN = decltype(mean_t)::value;
@@ -1016,7 +1178,11 @@ static void launch_csr_lookup_forward_t(const PT* params, const int64_t* values,
                              block, 0, stream, params, values, splits,
                              per_id_w, out, num_rows, vocab, width,
                              long_thresh, long_rows, long_count, t.tile_w);
-        if constexpr (kFloatOut)
+        if (det.slab != nullptr)
+          launch_forward_long_pass_det<TILE, VEC, MEAN, HAS_W>(
+              params, values, splits, per_id_w, out, vocab, width, long_rows,
+              long_count, work_items, n_work, t.tile_w, det, stream);
+        else if constexpr (kFloatOut)
           launch_forward_long_pass<TILE, VEC, MEAN, HAS_W>(
               params, values, splits, per_id_w, (float*)out, vocab, width,
               long_rows, long_count, work_items, n_work, t.tile_w, stream);
@@ -1031,7 +1197,9 @@ void launch_csr_lookup_forward(const void* params, bool params_bf16,
                                int64_t num_rows, int64_t nnz, int64_t vocab,
                                int width, bool mean, int64_t* long_rows,
                                int32_t* long_count, int64_t* work_items,
-                               int32_t* n_work, hipStream_t stream) {
+                               int32_t* n_work, float* det_slab,
+                               int32_t* det_work_base, hipStream_t stream) {
+  const DetBuffers det{det_slab, det_work_base};
   dispatch_bool(params_bf16, [&](auto p_bf16) {
     dispatch_bool(out_bf16, [&](auto o_bf16) {
       using PT = storage_t<decltype(p_bf16)>;
@@ -1039,7 +1207,7 @@ void launch_csr_lookup_forward(const void* params, bool params_bf16,
       launch_csr_lookup_forward_t((const PT*)params, values, splits, per_id_w,
                                   (OT*)out, num_rows, nnz, vocab, width, mean,
                                   long_rows, long_count, work_items, n_work,
-                                  stream);
+                                  det, stream);
     });
   });
 }
@@ -1063,14 +1231,14 @@ static void launch_csr_lookup_forward_packed_t(
     const float* per_id_w, OT* out, int64_t num_rows, int64_t nnz,
     int64_t vocab, int width, bool mean, int64_t* long_rows,
     int32_t* long_count, int64_t* work_items, int32_t* n_work,
-    hipStream_t stream) {
+    const DetBuffers& det, hipStream_t stream) {
   constexpr bool kFloatOut = std::is_same<OT, float>::value;
   const dim3 block(256);
   reset_long_lists(long_count, n_work, stream);
   const RowTiling t = row_tiling<0, VEC>(width, num_rows);
   const dim3 grid(pick_grid(t.row_waves, block.x / WAVE));
-  const int64_t long_thresh =
-      forward_long_threshold(t.row_waves, nnz, num_rows, kFloatOut);
+  const int64_t long_thresh = forward_long_threshold(
+      t.row_waves, nnz, num_rows, kFloatOut || det.slab != nullptr);
   dispatch_bool(mean, [&](auto mean_t) {
     dispatch_bool(per_id_w != nullptr, [&](auto has_w_t) {
       constexpr bool MEAN = decltype(mean_t)::value;
@@ -1079,7 +1247,11 @@ static void launch_csr_lookup_forward_packed_t(
                          0, stream, params, values, splits, per_id_w, out,
                          num_rows, vocab, width, long_thresh, long_rows,
                          long_count, t.tile_w);
-      if constexpr (kFloatOut)
+      if (det.slab != nullptr)
+        launch_forward_long_pass_det<0, VEC, MEAN, HAS_W>(
+            params, values, splits, per_id_w, out, vocab, width, long_rows,
+            long_count, work_items, n_work, t.tile_w, det, stream);
+      else if constexpr (kFloatOut)
         launch_forward_long_pass<0, VEC, MEAN, HAS_W>(
             params, values, splits, per_id_w, (float*)out, vocab, width,
             long_rows, long_count, work_items, n_work, t.tile_w, stream);
@@ -1093,12 +1265,15 @@ void launch_csr_lookup_forward_q8(const void* packed, const int64_t* values,
                                   int64_t nnz, int64_t vocab, int width,
                                   bool mean, int64_t* long_rows,
                                   int32_t* long_count, int64_t* work_items,
-                                  int32_t* n_work, hipStream_t stream) {
+                                  int32_t* n_work, float* det_slab,
+                                  int32_t* det_work_base, hipStream_t stream) {
+  const DetBuffers det{det_slab, det_work_base};
   dispatch_bool(out_bf16, [&](auto o_bf16) {
     using OT = storage_t<decltype(o_bf16)>;
     launch_csr_lookup_forward_packed_t<4>(
         (const q8_t*)packed, values, splits, per_id_w, (OT*)out, num_rows, nnz,
-        vocab, width, mean, long_rows, long_count, work_items, n_work, stream);
+        vocab, width, mean, long_rows, long_count, work_items, n_work, det,
+        stream);
   });
 }
 
@@ -1108,12 +1283,15 @@ void launch_csr_lookup_forward_q4(const void* packed, const int64_t* values,
                                   int64_t nnz, int64_t vocab, int width,
                                   bool mean, int64_t* long_rows,
                                   int32_t* long_count, int64_t* work_items,
-                                  int32_t* n_work, hipStream_t stream) {
+                                  int32_t* n_work, float* det_slab,
+                                  int32_t* det_work_base, hipStream_t stream) {
+  const DetBuffers det{det_slab, det_work_base};
   dispatch_bool(out_bf16, [&](auto o_bf16) {
     using OT = storage_t<decltype(o_bf16)>;
     launch_csr_lookup_forward_packed_t<8>(
         (const q4_t*)packed, values, splits, per_id_w, (OT*)out, num_rows, nnz,
-        vocab, width, mean, long_rows, long_count, work_items, n_work, stream);
+        vocab, width, mean, long_rows, long_count, work_items, n_work, det,
+        stream);
   });
 }
 
@@ -1823,7 +2001,11 @@ __global__ void sorted_opt_update_rowwise(
 
 // Long segments, fp32 SGD: chunk partials atomically into the weight
 // (linear).  Otherwise: chunk partials into fp32 scratch rows, then finalize.
-template <int TILE, int VEC, bool HAS_W, bool TO_SCRATCH, typename GT>
+// DET (deterministic mode, TO_SCRATCH only): target is the slab and item
+// `item` stores its partial to slab row `item` with plain stores; the
+// fixed-order combine then completes the scratch rows (see csr_fwd_long).
+template <int TILE, int VEC, bool HAS_W, bool TO_SCRATCH, bool DET,
+          typename GT>
 __global__ void sorted_opt_long(float* __restrict__ target,  // weight or scratch
                                 const int64_t* __restrict__ sorted_ids,
                                 const int64_t* __restrict__ seg,
@@ -1845,21 +2027,29 @@ __global__ void sorted_opt_long(float* __restrict__ target,  // weight or scratc
     if (item >= n_items) continue;
     const LongChunk c = long_chunk(work_items, long_rows, seg, item);
     if (c.ks >= c.e) continue;
+    static_assert(TO_SCRATCH || !DET, "the slab feeds the scratch rows");
     float* trow =
-        target + (TO_SCRATCH ? c.li : sorted_ids[c.s]) * (int64_t)width;
+        target + (DET ? item : TO_SCRATCH ? c.li : sorted_ids[c.s]) *
+                     (int64_t)width;
     if constexpr (TILE > 0) {
       const float g = narrow_reduce<TILE, WAVE / TILE, 2, HAS_W, false>(
           grad_out, srow, sw, 0, width, c.ks, c.ke, wc.lane);
-      if (wc.lane < TILE && wc.lane < width)
-        atomicAdd(&trow[wc.lane], TO_SCRATCH ? g : -lr * g);
+      if (wc.lane < TILE && wc.lane < width) {
+        if constexpr (DET) trow[wc.lane] = g;
+        else atomicAdd(&trow[wc.lane], TO_SCRATCH ? g : -lr * g);
+      }
     } else {
       for (int col0 = tc.tl * VEC; col0 < width; col0 += tile_w * VEC) {
         float acc[VEC];
         wide_accumulate<VEC, HAS_W, false>(grad_out, srow, sw, 0, width, col0,
                                            c.ks, c.ke, acc);
+        if constexpr (DET) {
+          pt_storev<VEC>(trow + col0, acc);
+        } else {
 #pragma unroll
-        for (int v = 0; v < VEC; ++v)
-          atomicAdd(&trow[col0 + v], TO_SCRATCH ? acc[v] : -lr * acc[v]);
+          for (int v = 0; v < VEC; ++v)
+            atomicAdd(&trow[col0 + v], TO_SCRATCH ? acc[v] : -lr * acc[v]);
+        }
       }
     }
   }
@@ -1944,12 +2134,15 @@ static void launch_sorted_optimizer_update_t(
     const GT* grad_out, const float* lr, const int32_t* nu_ptr,
     int64_t max_segs, int width, int64_t* long_rows, int32_t* long_count,
     int64_t* work_items, int32_t* n_work, float* long_scratch, int rule,
-    bool rowwise, const int64_t* sr, AdamArgs ad, hipStream_t stream) {
+    bool rowwise, const int64_t* sr, AdamArgs ad, const DetBuffers& det,
+    hipStream_t stream) {
   const dim3 block(256);
+  const bool deterministic = det.slab != nullptr;
   // bf16 weights have no atomicAdd: their long-SGD path also goes through the
-  // fp32 scratch + finalize pair.
-  const bool use_scratch =
-      rule != RULE_SGD || !std::is_same<PT, float>::value;
+  // fp32 scratch + finalize pair.  So does every rule in deterministic mode,
+  // where the combine completes the scratch rows.
+  const bool use_scratch = deterministic || rule != RULE_SGD ||
+                           !std::is_same<PT, float>::value;
   dispatch_width(width, [&](auto tile, auto vec) {
     constexpr int TILE = decltype(tile)::value, VEC = decltype(vec)::value;
     const RowTiling t = row_tiling<TILE, VEC>(width, max_segs);
@@ -1972,15 +2165,28 @@ static void launch_sorted_optimizer_update_t(
               long_rows, long_count, t.tile_w, sr, ad);
         });
       }
-      hipLaunchKernelGGL(expand_long_work, dim3(512), block, 0, stream,
-                         long_rows, long_count, seg, work_items, n_work);
+      if (deterministic) {
+        hipLaunchKernelGGL(expand_long_work<true>, dim3(512), block, 0, stream,
+                           long_rows, long_count, seg, work_items, n_work,
+                           det.work_base);
+        hipLaunchKernelGGL(
+            (sorted_opt_long<TILE, VEC, HAS_W, true, true, GT>), dim3(2048),
+            block, 0, stream, det.slab, sorted_ids, seg, srow, sw, grad_out,
+            lr, width, long_rows, work_items, n_work, t.tile_w);
+        launch_slab_combine<true>(det, long_scratch, width, long_rows,
+                                  long_count, seg, work_items, n_work, stream);
+        return;
+      }
+      hipLaunchKernelGGL(expand_long_work<false>, dim3(512), block, 0, stream,
+                         long_rows, long_count, seg, work_items, n_work,
+                         (int32_t*)nullptr);
       dispatch_bool(use_scratch, [&](auto to_scratch) {
         constexpr bool TO_SCRATCH = decltype(to_scratch)::value;
         hipLaunchKernelGGL(
-            (sorted_opt_long<TILE, VEC, HAS_W, TO_SCRATCH, GT>), dim3(2048),
-            block, 0, stream, TO_SCRATCH ? long_scratch : (float*)weight,
-            sorted_ids, seg, srow, sw, grad_out, lr, width, long_rows,
-            work_items, n_work, t.tile_w);
+            (sorted_opt_long<TILE, VEC, HAS_W, TO_SCRATCH, false, GT>),
+            dim3(2048), block, 0, stream,
+            TO_SCRATCH ? long_scratch : (float*)weight, sorted_ids, seg, srow,
+            sw, grad_out, lr, width, long_rows, work_items, n_work, t.tile_w);
       });
     });
     if (rowwise)
@@ -2009,10 +2215,12 @@ void launch_sorted_optimizer_update(void* weight, bool weight_bf16,
                                     int64_t* work_items, int32_t* n_work,
                                     float* long_scratch, int64_t scratch_rows,
                                     bool adagrad, bool rowwise, int64_t* sr,
-                                    const AdamConfig* adam,
+                                    const AdamConfig* adam, float* det_slab,
+                                    int32_t* det_work_base,
                                     hipStream_t stream) {
   if (!weight_bf16) sr = nullptr;  // fp32 tables do not round
   const int rule = adam ? RULE_ADAM : adagrad ? RULE_ADAGRAD : RULE_SGD;
+  const DetBuffers det{det_slab, det_work_base};
   if (adam) {
     hipLaunchKernelGGL(adam_advance_step, dim3(1), dim3(WAVE), 0, stream,
                        adam->step, lr, adam->a_t, adam->b1, adam->b2);
@@ -2020,7 +2228,8 @@ void launch_sorted_optimizer_update(void* weight, bool weight_bf16,
   }
   hipMemsetAsync(long_count, 0, sizeof(int32_t), stream);
   hipMemsetAsync(n_work, 0, sizeof(int32_t), stream);
-  if (long_scratch) {
+  // the deterministic combine stores whole scratch rows: nothing to zero
+  if (long_scratch && !det.slab) {
     hipMemsetAsync(long_scratch, 0,
                    sizeof(float) * scratch_rows * (int64_t)width, stream);
   }
@@ -2033,7 +2242,7 @@ void launch_sorted_optimizer_update(void* weight, bool weight_bf16,
             (PT*)weight, state, eps, sorted_ids, seg, srow, sw,
             (const GT*)grad_out, lr, nu_ptr, max_segs, width, long_rows,
             long_count, work_items, n_work, long_scratch, rule,
-            rowwise && !adam, sr, adam_args(adam, width), stream);
+            rowwise && !adam, sr, adam_args(adam, width), det, stream);
       });
     });
   });

@@ -13,7 +13,15 @@ void launch_csr_lookup_forward(const void* params, bool params_bf16,
                                int64_t num_rows, int64_t nnz, int64_t vocab,
                                int width, bool mean, int64_t* long_rows,
                                int32_t* long_count, int64_t* work_items,
-                               int32_t* n_work, hipStream_t stream);
+                               int32_t* n_work, float* det_slab,
+                               int32_t* det_work_base, hipStream_t stream);
+
+// Deterministic mode (all forwards and launch_sorted_optimizer_update):
+// det_slab, fp32 [work_items capacity, width], and det_work_base, int32
+// [long_rows capacity], select it; both null keep the atomic long-row
+// combine.  With them every long row's 128-id chunk partials go to the slab
+// and are added in a fixed order (docs/KERNELS.md), bf16-out forwards split
+// long rows like fp32-out ones, and no float atomic is issued.
 
 // int8 row-wise quantized tables.  packed is [vocab, width + 8] bytes: per
 // row width bytes q, fp32 scale, fp32 bias; the row stands for
@@ -24,7 +32,8 @@ void launch_csr_lookup_forward_q8(const void* packed, const int64_t* values,
                                   int64_t nnz, int64_t vocab, int width,
                                   bool mean, int64_t* long_rows,
                                   int32_t* long_count, int64_t* work_items,
-                                  int32_t* n_work, hipStream_t stream);
+                                  int32_t* n_work, float* det_slab,
+                                  int32_t* det_work_base, hipStream_t stream);
 // in: [n, width] fp32 or bf16, aligned to four elements; packed:
 // [n, width + 8].
 void launch_quantize_rows_q8(const void* in, bool in_bf16, void* packed,
@@ -42,7 +51,8 @@ void launch_csr_lookup_forward_q4(const void* packed, const int64_t* values,
                                   int64_t nnz, int64_t vocab, int width,
                                   bool mean, int64_t* long_rows,
                                   int32_t* long_count, int64_t* work_items,
-                                  int32_t* n_work, hipStream_t stream);
+                                  int32_t* n_work, float* det_slab,
+                                  int32_t* det_work_base, hipStream_t stream);
 // in: [n, width] fp32 or bf16, aligned to four elements; packed:
 // [n, width / 2 + 4].
 void launch_quantize_rows_q4(const void* in, bool in_bf16, void* packed,
@@ -131,6 +141,8 @@ struct AdamConfig {
 // reads the same step and a trailing one-thread kernel adds 1 to it, which is
 // why the pointer is not const.  nullptr (and any fp32 weight) keeps
 // round-to-nearest-even and launches nothing extra.
+// det_slab / det_work_base: deterministic mode, see above.  long_scratch is
+// then needed for every rule, fp32 SGD included.
 void launch_sorted_optimizer_update(void* weight, bool weight_bf16,
                                     float* state, float eps,
                                     const int64_t* sorted_ids,
@@ -143,7 +155,8 @@ void launch_sorted_optimizer_update(void* weight, bool weight_bf16,
                                     int64_t* work_items, int32_t* n_work,
                                     float* long_scratch, int64_t scratch_rows,
                                     bool adagrad, bool rowwise, int64_t* sr,
-                                    const AdamConfig* adam,
+                                    const AdamConfig* adam, float* det_slab,
+                                    int32_t* det_work_base,
                                     hipStream_t stream);
 
 void launch_sparse_row_update(void* weight, bool weight_bf16, float* state,

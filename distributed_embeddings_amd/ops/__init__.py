@@ -1,5 +1,6 @@
 from .embedding_lookup import (Ragged, dequantize_rowwise_int4,
-                               dequantize_rowwise_int8, embedding_lookup,
+                               dequantize_rowwise_int8, deterministic,
+                               embedding_lookup, is_deterministic,
                                quantize_rowwise_int4, quantize_rowwise_int8,
                                quantized_embedding_lookup, row_to_split,
-                               stochastic_round_bf16)
+                               set_deterministic, stochastic_round_bf16)

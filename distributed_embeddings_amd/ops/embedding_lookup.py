@@ -17,11 +17,67 @@ their summed gradient rows — so sparse-capable optimizers (SGD/Adagrad/
 SparseAdam) apply O(nnz) updates.
 """
 
+import contextlib
+import os
 from typing import NamedTuple, Optional, Sequence, Tuple, Union
 
 import torch
 
 from . import _backend
+
+
+# ---------------------------------------------------------------------------
+# Deterministic mode
+# ---------------------------------------------------------------------------
+#
+# The HIP kernels split a segment of more than 128 ids -- a long bag of the
+# forward, a hot id of the sparse backward and of the fused optimizers -- into
+# 128-id chunks.  By default the chunk partials meet in fp32 atomics, whose
+# order, and with it the last bits of the sum, changes from run to run.  In
+# deterministic mode each partial goes to a slab row of its own and the rows
+# are added in a fixed order (docs/KERNELS.md, "Deterministic mode"), so the
+# lookup forward, the sparse backward and the fused optimizers issue no float
+# atomic and repeat bit for bit.  The initial value comes from
+# DE_DETERMINISTIC=1.  The mode is independent of
+# torch.use_deterministic_algorithms.
+
+_deterministic = os.environ.get("DE_DETERMINISTIC", "0") == "1"
+
+
+def set_deterministic(flag: bool) -> None:
+    """Turns the deterministic mode of the lookup kernels on or off.
+
+    With the mode on, long segments (more than 128 ids) are combined in a
+    fixed order and the lookup forward (fp32, bf16, int8 and int4 tables),
+    the sparse backward and the fused optimizers issue no float atomic: equal
+    inputs give equal bits on every run.  bf16-out forwards then split long
+    bags like fp32-out ones.  A forward reads the flag when it runs; its
+    backward uses the mode its forward saw.
+
+    On the CPU the flag is accepted and changes nothing: those paths already
+    add in a fixed order.  Not covered: the value a new key draws in
+    ``IntegerLookup``, the reduction order inside collectives, and torch's
+    own ops.
+    """
+    global _deterministic
+    _deterministic = bool(flag)
+
+
+def is_deterministic() -> bool:
+    """Whether the deterministic mode is on (see :func:`set_deterministic`)."""
+    return _deterministic
+
+
+@contextlib.contextmanager
+def deterministic(flag: bool = True):
+    """Context manager: the deterministic mode set to ``flag`` inside the
+    block and back to its previous value after it."""
+    previous = is_deterministic()
+    set_deterministic(flag)
+    try:
+        yield
+    finally:
+        set_deterministic(previous)
 
 
 class Ragged(NamedTuple):
@@ -172,12 +228,15 @@ class _CsrLookup(torch.autograd.Function):
         ctx.width = weight.shape[1]
         ctx.wdtype = weight.dtype
         ctx.dw_dtype = per_id_w.dtype if need_dw else None
+        # the backward runs in the mode the forward saw
+        ctx.deterministic = is_deterministic()
         if weight.is_cuda:
             # bf16 out is stored directly by the kernel (no cast kernel);
             # the backward consumes bf16 grads natively too
             return _backend.ops().csr_lookup_forward(
                 weight, values, row_splits, combiner == "mean",
-                out_dtype == torch.bfloat16, w32)
+                out_dtype == torch.bfloat16, w32,
+                deterministic=ctx.deterministic)
         out = _csr_lookup_ref(weight, values, row_splits, combiner, w32)
         return out.to(out_dtype) if out_dtype is not None else out
 
@@ -188,7 +247,8 @@ class _CsrLookup(torch.autograd.Function):
         if grad_out.is_cuda:
             unique_ids, unique_grad = _backend.ops().csr_lookup_backward(
                 grad_out, values, row_splits, ctx.vocab,
-                ctx.combiner == "mean", w32
+                ctx.combiner == "mean", w32,
+                deterministic=ctx.deterministic
             )
         else:
             unique_ids, unique_grad = _csr_lookup_backward_ref(
@@ -475,10 +535,13 @@ class _CsrLookupFusedOptimizer(torch.autograd.Function):
         ctx.adagrad = adagrad
         ctx.eps = eps
         ctx.dw_dtype = per_id_w.dtype if need_dw else None
+        # the backward runs in the mode the forward saw
+        ctx.deterministic = is_deterministic()
         if weight.is_cuda:
             return _backend.ops().csr_lookup_forward(
                 weight, values, row_splits, combiner == "mean",
-                out_dtype == torch.bfloat16, w32)
+                out_dtype == torch.bfloat16, w32,
+                deterministic=ctx.deterministic)
         out = _csr_lookup_ref(weight, values, row_splits, combiner, w32)
         return out.to(out_dtype) if out_dtype is not None else out
 
@@ -500,11 +563,13 @@ class _CsrLookupFusedOptimizer(torch.autograd.Function):
                 _backend.ops().csr_fused_optimizer_apply(
                     weight, state, values, row_splits, grad_out, lr,
                     ctx.combiner == "mean", False, ctx.eps, w32, sr,
-                    adam_step=adam[0], beta1=adam[1], beta2=adam[2])
+                    adam_step=adam[0], beta1=adam[1], beta2=adam[2],
+                    deterministic=ctx.deterministic)
             elif weight.is_cuda:
                 _backend.ops().csr_fused_optimizer_apply(
                     weight, state, values, row_splits, grad_out, lr,
-                    ctx.combiner == "mean", ctx.adagrad, ctx.eps, w32, sr)
+                    ctx.combiner == "mean", ctx.adagrad, ctx.eps, w32, sr,
+                    deterministic=ctx.deterministic)
             else:
                 unique_ids, unique_grad = _csr_lookup_backward_ref(
                     grad_out.float(), values, row_splits, weight.shape[0],
@@ -893,7 +958,8 @@ def _csr_lookup_q8(packed, values, row_splits, combiner, out_dtype=None,
         forward = (ext.csr_lookup_forward_q4 if bits == 4
                    else ext.csr_lookup_forward_q8)
         return forward(packed, values, row_splits, combiner == "mean",
-                       out_dtype == torch.bfloat16, w32)
+                       out_dtype == torch.bfloat16, w32,
+                       deterministic=is_deterministic())
     vocab = packed.shape[0]
     valid = (values >= 0) & (values < vocab)
     # dequantize only the rows the batch touches, and append one zero row:

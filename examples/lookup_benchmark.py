@@ -5,6 +5,9 @@ step vs the plain-PyTorch equivalent.
 Capability parity with the reference ``examples/benchmarks/benchmark.py:23-98``
 (voc=1e6, width=128, batch=16384, hotness<=500).
 
+``--deterministic`` turns the deterministic mode on for the whole run (long
+bags are then combined in a fixed order, without float atomics).
+
 ``--table-dtype int8`` times the forward only, from an int8 row-wise quantized
 table next to the fp32 one it was made from (quantized tables do not train).
 """
@@ -18,7 +21,9 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 import torch
 
-from distributed_embeddings_amd import Embedding, Ragged, SparseEmbeddingOptimizer
+from distributed_embeddings_amd import (Embedding, Ragged,
+                                        SparseEmbeddingOptimizer,
+                                        set_deterministic)
 
 
 def timeit(fn, iters=20, warmup=5):
@@ -45,7 +50,10 @@ def main():
     p.add_argument("--table-dtype", default="fp32", choices=["fp32", "int8"],
                    help="int8: forward-only measurement from the row-wise "
                         "quantized table")
+    p.add_argument("--deterministic", action="store_true",
+                   help="run in deterministic mode")
     args = p.parse_args()
+    set_deterministic(args.deterministic)
     device = "cuda" if torch.cuda.is_available() else "cpu"
 
     g = torch.Generator().manual_seed(0)

@@ -12,6 +12,7 @@ per (ids, method, rounding).
   python tools/bench_fused_update.py --methods adagrad lazy_adam
   python tools/bench_fused_update.py --ext OTHER/_hip_ops*.so --methods sgd adagrad
   python tools/bench_fused_update.py --table-dtype bf16 --stochastic-rounding
+  python tools/bench_fused_update.py --deterministic --id-sets power_law all_equal
 
 --ext times another build of the extension (e.g. the parent commit's) on the
 same inputs.  --stochastic-rounding (bf16 tables) times every method twice,
@@ -19,6 +20,12 @@ with nearest-even and with stochastic rounding, the two alternating inside
 every round like the methods.  lazy_adam needs this tree's build: its state
 is the [2, VOCAB, WIDTH] moments (10 GB) and it counts its steps in a device
 tensor.
+
+--deterministic times this tree's build in deterministic mode (long segments
+through the slab and the fixed-order combine, no float atomics); the line then
+carries the slab's size.  --id-sets picks the id distributions: besides the
+two defaults, tiny_vocab (8192 ids over a vocabulary of 3) and all_equal (all
+1.7M ids the same), the extremes of the long-segment path.
 """
 import argparse
 import importlib.util
@@ -33,6 +40,7 @@ import torch
 
 VOCAB, WIDTH, NNZ = 10_000_000, 128, 1_700_000
 METHODS = ("sgd", "adagrad", "rowwise_adagrad", "lazy_adam")
+ID_SETS = ("uniform", "power_law", "tiny_vocab", "all_equal")
 
 
 def load_ext(path):
@@ -64,10 +72,16 @@ def main():
     p.add_argument("--table-dtype", choices=("fp32", "bf16"), default="fp32")
     p.add_argument("--stochastic-rounding", action="store_true",
                    help="also time stochastic rounding (needs bf16 tables)")
+    p.add_argument("--deterministic", action="store_true",
+                   help="time the deterministic mode (this tree's build only)")
+    p.add_argument("--id-sets", nargs="+", default=["uniform", "power_law"],
+                   choices=ID_SETS)
     args = p.parse_args()
     assert torch.cuda.is_available(), "needs a GPU: no timing without one"
     if args.stochastic_rounding and args.table_dtype != "bf16":
         p.error("--stochastic-rounding needs --table-dtype bf16")
+    if args.deterministic and args.ext:
+        p.error("--deterministic times this tree's build, not --ext")
     ext = load_ext(args.ext)
     from distributed_embeddings_amd.utils.input_gen import power_law_ids
 
@@ -75,13 +89,18 @@ def main():
     w = torch.randn(VOCAB, WIDTH, device="cuda")
     if args.table_dtype == "bf16":
         w = w.bfloat16()
-    splits = torch.arange(NNZ + 1, device="cuda")
-    grad = torch.randn(NNZ, WIDTH, device="cuda").bfloat16()
+    all_splits = torch.arange(NNZ + 1, device="cuda")
+    all_grad = torch.randn(NNZ, WIDTH, device="cuda").bfloat16()
     lr = torch.tensor([1e-3], device="cuda")
-    id_sets = {
-        "uniform": torch.randint(0, VOCAB, (NNZ,), device="cuda"),
-        "power_law": power_law_ids(VOCAB, (NNZ,), 1.05).cuda(),
+    make_ids = {
+        "uniform": lambda: torch.randint(0, VOCAB, (NNZ,), device="cuda"),
+        "power_law": lambda: power_law_ids(VOCAB, (NNZ,), 1.05).cuda(),
+        "tiny_vocab": lambda: torch.randint(0, 3, (8192,), device="cuda"),
+        "all_equal": lambda: torch.full((NNZ,), 12345, device="cuda"),
     }
+    id_sets = {name: make_ids[name]() for name in args.id_sets}
+    # the parent commit's call, argument for argument, unless asked otherwise
+    det = {"deterministic": True} if args.deterministic else {}
     states = {m: state_for(m) for m in args.methods}
     sr = torch.tensor([1234, 0], device="cuda")  # {seed, step}
     adam_step = torch.zeros(1, dtype=torch.int64, device="cuda")
@@ -90,15 +109,18 @@ def main():
 
     def call(variant, ids):
         method, rounding = variant
+        n = ids.numel()
+        splits, grad = all_splits[:n + 1], all_grad[:n]
         # the nearest-even call is the parent commit's, argument for argument
         extra = (None, sr) if rounding == "sr" else ()
         if method == "lazy_adam":
             ext.csr_fused_optimizer_apply(w, states[method], ids, splits, grad,
                                           lr, False, False, 1e-8, *extra,
-                                          adam_step=adam_step)
+                                          adam_step=adam_step, **det)
             return
         ext.csr_fused_optimizer_apply(w, states[method], ids, splits, grad, lr,
-                                      False, method != "sgd", 1e-10, *extra)
+                                      False, method != "sgd", 1e-10, *extra,
+                                      **det)
 
     for name, ids in id_sets.items():
         for v in variants:
@@ -125,6 +147,9 @@ def main():
                 "us_min": round(min(times[v]), 1),
                 "us_max": round(max(times[v]), 1),
                 "state_bytes": states[v[0]].numel() * 4,
+                "deterministic": args.deterministic,
+                "slab_bytes": ((ids.numel() // 64 + 64) * WIDTH * 4
+                               if args.deterministic else 0),
             }), flush=True)
 
 
