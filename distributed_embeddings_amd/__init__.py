@@ -12,7 +12,7 @@ Public API (parity: reference ``distributed_embeddings/__init__.py:17-27``):
 from .ops.embedding_lookup import (Ragged, dequantize_rowwise_int4,
                                    dequantize_rowwise_int8, deterministic,
                                    embedding_lookup, is_deterministic,
-                                   quantize_rowwise_int4,
+                                   multi_hot_expand, quantize_rowwise_int4,
                                    quantize_rowwise_int8,
                                    quantized_embedding_lookup, row_to_split,
                                    set_deterministic, stochastic_round_bf16)
@@ -44,6 +44,7 @@ __all__ = [
     "dequantize_rowwise_int4",
     "quantized_embedding_lookup",
     "stochastic_round_bf16",
+    "multi_hot_expand",
     "set_deterministic",
     "is_deterministic",
     "deterministic",

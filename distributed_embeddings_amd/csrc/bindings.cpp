@@ -875,6 +875,63 @@ torch::Tensor stochastic_round_bf16(torch::Tensor x, int64_t seed,
   return out;
 }
 
+// The flat id vector of one fused lookup group, one segment per list entry in
+// order (csrc/pack_ids.hip).  expand[i] false: srcs[i] holds rows * h_out[i]
+// ids that are copied; true: srcs[i] holds one id per row and each is expanded
+// to h_out[i] ids with (vocab[i], key_f[i]).  offset[i] is added to every id
+// of the segment.  key_f carries a uint64 bit pattern.
+torch::Tensor pack_ids(std::vector<torch::Tensor> srcs,
+                       std::vector<int64_t> h_out, std::vector<bool> expand,
+                       std::vector<int64_t> vocab, std::vector<int64_t> key_f,
+                       std::vector<int64_t> offset) {
+  const size_t nseg = srcs.size();
+  TORCH_CHECK(nseg >= 1, "pack_ids needs at least one segment");
+  TORCH_CHECK(h_out.size() == nseg && expand.size() == nseg &&
+                  vocab.size() == nseg && key_f.size() == nseg &&
+                  offset.size() == nseg,
+              "pack_ids: every list must have one entry per segment");
+  TORCH_CHECK(nseg <= (size_t)INT32_MAX, "pack_ids: too many segments");
+  std::vector<PackIdsSegment> segs(nseg);
+  int64_t total = 0;
+  for (size_t i = 0; i < nseg; ++i) {
+    const auto& src = srcs[i];
+    TORCH_CHECK(src.is_cuda(), "pack_ids: segment ", i, " must be on GPU");
+    TORCH_CHECK(src.device() == srcs[0].device(),
+                "pack_ids: all segments must be on the same device");
+    TORCH_CHECK(src.dtype() == torch::kInt64,
+                "pack_ids: segment ", i, " must be int64");
+    TORCH_CHECK(src.is_contiguous(),
+                "pack_ids: segment ", i, " must be contiguous");
+    TORCH_CHECK(h_out[i] >= 1 && h_out[i] <= INT32_MAX,
+                "pack_ids: h_out must be >= 1 (segment ", i, ")");
+    PackIdsSegment& s = segs[i];
+    s.src = src.data_ptr<int64_t>();
+    s.h_out = (int32_t)h_out[i];
+    if (expand[i]) {
+      TORCH_CHECK(vocab[i] >= 1,
+                  "pack_ids: an expand segment needs vocab >= 1");
+      s.mode = kPackIdsExpand;
+      s.rows = src.numel();
+    } else {
+      TORCH_CHECK(src.numel() % h_out[i] == 0, "pack_ids: segment ", i,
+                  " does not hold whole rows of ", h_out[i], " ids");
+      s.mode = kPackIdsCopy;
+      s.rows = src.numel() / h_out[i];
+    }
+    s.vocab = vocab[i];
+    s.key_f = (uint64_t)key_f[i];
+    s.offset = offset[i];
+    s.dst_begin = total;
+    total += s.rows * h_out[i];
+  }
+  auto out = torch::empty({total}, srcs[0].options());
+  if (total > 0) {
+    launch_pack_ids(segs.data(), (int)nseg, out.data_ptr<int64_t>(),
+                    current_stream());
+  }
+  return out;
+}
+
 // Shapes the interaction kernels take: the 32-row kernels serve F <= 32, the
 // 64-row kernels 33 <= F <= 64 at D <= 256 (their LDS block).
 static void check_dot_interact_shape(int64_t F, int64_t D) {
@@ -1263,6 +1320,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "fp32 -> bf16 with the fused optimizers' stochastic rounding (gfx950)",
         pybind11::arg("x"), pybind11::arg("seed"), pybind11::arg("step") = 0,
         pybind11::arg("base_offset") = 0);
+  m.def("pack_ids", &pack_ids,
+        "flat id vector of a fused lookup group from copy / multi-hot expand "
+        "segments, one pass (gfx950)",
+        pybind11::arg("srcs"), pybind11::arg("h_out"), pybind11::arg("expand"),
+        pybind11::arg("vocab"), pybind11::arg("key_f"),
+        pybind11::arg("offset"));
   m.def("dot_interact_fwd_packed", &dot_interact_fwd_packed,
         "pairwise-dot interaction on (bottom, packed, perm) (MFMA, gfx950)");
   m.def("dot_interact_bwd_packed", &dot_interact_bwd_packed,

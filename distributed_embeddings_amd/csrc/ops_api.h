@@ -171,6 +171,31 @@ void launch_stochastic_round_bf16(const float* x, void* out, int64_t n,
                                   int64_t seed, int64_t step,
                                   int64_t base_offset, hipStream_t stream);
 
+// pack_ids.hip.  One segment of a pack_ids launch: the ids of one (input,
+// slice) pair of a fused lookup group.  copy: src is [rows, h_out] and
+// dst[dst_begin + r * h_out + k] = src[r, k] + offset.  expand: src is [rows]
+// and the k-th id of row r is the multi-hot expansion of src[r] (see
+// pack_ids.hip) + offset.  h_out >= 1; expand needs vocab >= 1.
+constexpr int kPackIdsCopy = 0;
+constexpr int kPackIdsExpand = 1;
+constexpr int kPackIdsMaxSegments = 64;  // per launch: 56 bytes each, < 4 KB
+struct PackIdsSegment {
+  const int64_t* src;
+  int64_t rows;
+  int64_t dst_begin;
+  int64_t vocab;
+  uint64_t key_f;
+  int64_t offset;
+  int32_t h_out;
+  int32_t mode;
+};
+// The segments go by value in the kernel arguments, kPackIdsMaxSegments per
+// launch, so nseg above that takes several launches over consecutive
+// segments.  Segments with rows == 0 are legal, and a call whose segments are
+// all empty launches nothing.  dst must be 8-byte aligned.
+void launch_pack_ids(const PackIdsSegment* segs, int nseg, int64_t* dst,
+                     hipStream_t stream);
+
 void launch_dot_interact_fwd_packed(const void* bottom, const void* packed,
                                     const int* perm, void* out, int64_t B,
                                     int F, int D, int out_w, int tri_n,

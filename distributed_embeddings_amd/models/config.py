@@ -30,6 +30,12 @@ class ModelConfig:
     interact_stride: Optional[int]
 
 
+# Ids per sample of the 26 Criteo features in the public multi-hot
+# DLRM-DCNv2 benchmark model (214 in all); ``DLRM(multi_hot_sizes=...)``.
+MLPERF_MULTI_HOT_SIZES = [3, 2, 1, 2, 6, 1, 1, 1, 1, 7, 3, 8, 1, 6, 9, 5, 1, 1,
+                          1, 12, 100, 27, 10, 3, 1, 1]
+
+
 model_tiny = ModelConfig(
     name="tiny",
     embedding_configs=[

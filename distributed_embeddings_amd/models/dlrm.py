@@ -84,6 +84,14 @@ class DLRM(nn.Module):
       interaction: "dot" (pairwise dot products, the default) or "cross"
         (DCN-v2 low-rank cross network, DLRM-DCNv2).
       cross_layers / cross_rank: depth and rank of the cross network.
+      multi_hot_sizes: ids per sample and feature, one int >= 1 per table
+        (``models.config.MLPERF_MULTI_HOT_SIZES`` for the Criteo benchmark
+        model).  The tables then sum their bags (``combiner="sum"``) and a
+        one-hot input ``[B]`` is expanded on the device
+        (``DistributedEmbedding.set_multi_hot``); ``[B, h]`` inputs are
+        taken as they are.  None (default): one-hot tables without combiner.
+      multi_hot_seed: seed of the expansion; serve a model with the seed it
+        was trained with.
     """
 
     def __init__(
@@ -101,6 +109,8 @@ class DLRM(nn.Module):
         interaction: str = "dot",
         cross_layers: int = 3,
         cross_rank: int = 512,
+        multi_hot_sizes: Optional[Sequence[int]] = None,
+        multi_hot_seed: int = 0,
     ):
         super().__init__()
         if interaction not in ("dot", "cross"):
@@ -108,6 +118,13 @@ class DLRM(nn.Module):
                 f"interaction must be 'dot' or 'cross', got {interaction!r}")
         self.interaction = interaction
         self.table_sizes = list(table_sizes)
+        if multi_hot_sizes is not None and \
+                len(multi_hot_sizes) != len(self.table_sizes):
+            raise ValueError(
+                f"multi_hot_sizes needs one entry per table: got "
+                f"{len(multi_hot_sizes)} for {len(self.table_sizes)} tables")
+        self.multi_hot_sizes = None if multi_hot_sizes is None \
+            else [int(h) for h in multi_hot_sizes]
         self.embedding_dim = embedding_dim
         self.distributed = comm.world_size() > 1
         self.dp_input = dp_input
@@ -131,7 +148,9 @@ class DLRM(nn.Module):
 
         from ..parallel.strategy import TableConfig
         tables = [
-            TableConfig(s, embedding_dim, None, initializer=scaled_uniform_init)
+            TableConfig(s, embedding_dim,
+                        None if multi_hot_sizes is None else "sum",
+                        initializer=scaled_uniform_init)
             for s in table_sizes
         ]
         # DistributedEmbedding at every world size: at world==1 it still fuses
@@ -142,6 +161,8 @@ class DLRM(nn.Module):
             column_slice_threshold=column_slice_threshold,
             data_parallel_threshold=data_parallel_threshold,
             table_dtype=table_dtype)
+        if self.multi_hot_sizes is not None:
+            self.embeddings.set_multi_hot(self.multi_hot_sizes, multi_hot_seed)
 
         # packed interaction fast path: the fused-group lookup output (or the
         # a2a recv buffer) feeds dot_interact as one [F-1, B, D] view; the
@@ -187,7 +208,9 @@ class DLRM(nn.Module):
             # id exchange overlaps the MLP GEMMs (ids carry no grad)
             handle = self.embeddings.redistribute_async(cats)
         use_packed = self._dot_perm is not None and all(
-            isinstance(x, torch.Tensor) and x.dim() == 1 for x in cats)
+            isinstance(x, torch.Tensor)
+            and (x.dim() == 1 or (x.dim() == 2 and self.multi_hot_sizes))
+            for x in cats)
         want = torch.bfloat16 if (numerical.is_cuda and
                                   torch.is_autocast_enabled()) \
             else numerical.dtype

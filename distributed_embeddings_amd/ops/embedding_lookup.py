@@ -420,6 +420,129 @@ def stochastic_round_bf16(x: torch.Tensor, seed: int, step: int = 0,
     return _stochastic_round_bf16_ref(x, seed, step, offsets.view(x.shape))
 
 
+# ---------------------------------------------------------------------------
+# Multi-hot expansion and group id packing
+# ---------------------------------------------------------------------------
+#
+# A one-hot id x of feature f becomes a bag of `hotness` ids, a pure function
+# of (seed, f, x), all arithmetic mod 2**64:
+#
+#     key_f  = mix64(seed ^ mix64(f))
+#     inner  = mix64(key_f + x)
+#     bag[0] = x
+#     bag[k] = mix64(inner + k) % vocab        k = 1 .. hotness-1, unsigned
+#
+# An id outside [0, vocab) goes to every slot unhashed.  The numpy code below
+# is the definition and the CPU path; csrc/pack_ids.hip is tested against it
+# bit for bit.
+
+
+def multi_hot_key(seed: int, feature: int) -> int:
+    """``key_f`` of the expansion, as a Python int in [0, 2**64)."""
+    return mix64_int((int(seed) & _U64) ^ mix64_int(int(feature) & _U64))
+
+
+def _multi_hot_expand_np(ids: torch.Tensor, vocab: int, hotness: int,
+                         key_f: int) -> torch.Tensor:
+    import numpy as np
+    x = ids.detach().cpu().to(torch.int64).contiguous().numpy()
+    xu = x.astype(np.uint64)
+    out = np.empty(x.shape + (hotness,), dtype=np.int64)
+    out[..., :] = x[..., None]
+    valid = xu < np.uint64(vocab)
+    with np.errstate(over="ignore"):
+        inner = _mix64_np(xu + np.uint64(key_f))
+        for k in range(1, hotness):
+            hashed = _mix64_np(inner + np.uint64(k)) % np.uint64(vocab)
+            out[..., k] = np.where(valid, hashed.astype(np.int64), x)
+    return torch.from_numpy(out)
+
+
+def _check_multi_hot(vocab, hotness) -> None:
+    if int(vocab) < 1:
+        raise ValueError(f"vocab must be >= 1, got {vocab!r}")
+    if int(hotness) < 1:
+        raise ValueError(f"hotness must be >= 1, got {hotness!r}")
+
+
+def multi_hot_expand(ids: torch.Tensor, vocab: int, hotness: int, seed: int,
+                     feature: int = 0) -> torch.Tensor:
+    """Expands one-hot ``ids`` into bags: int64 ``[*ids.shape, hotness]``.
+
+    Slot 0 of a bag is the id itself; slot ``k`` is
+    ``mix64(mix64(key_f + id) + k) % vocab`` with
+    ``key_f = mix64(seed ^ mix64(feature))`` (unsigned 64-bit arithmetic,
+    ``mix64`` the splitmix64 finalizer the project uses elsewhere).  The bag
+    is a pure function of ``(seed, feature, id)``, uniform over the
+    vocabulary, and may hold duplicates.  An id outside ``[0, vocab)`` fills
+    every slot unhashed.  ``hotness == 1`` returns ``ids[..., None]``.
+
+    On the GPU this is the ``pack_ids`` HIP kernel, on the CPU numpy; the two
+    agree bit for bit.
+    """
+    _check_multi_hot(vocab, hotness)
+    return multi_hot_expand_keyed(ids, int(vocab), int(hotness),
+                                  multi_hot_key(seed, feature))
+
+
+def multi_hot_expand_keyed(ids: torch.Tensor, vocab: int, hotness: int,
+                           key_f: int) -> torch.Tensor:
+    """:func:`multi_hot_expand` with ``key_f`` (:func:`multi_hot_key`)
+    already formed."""
+    if hotness == 1:
+        return ids.to(torch.int64)[..., None]
+    if ids.is_cuda:
+        flat = pack_ids([(ids.detach().to(torch.int64).contiguous(),
+                          hotness, (vocab, key_f), 0)])
+        return flat.view(*ids.shape, hotness)
+    return _multi_hot_expand_np(ids, vocab, hotness, key_f)
+
+
+def pack_ids_enabled() -> bool:
+    """``DE_PACK_IDS`` (default on): build fused-group id vectors with the
+    ``pack_ids`` kernel instead of ``torch.cat`` + offset add."""
+    return os.environ.get("DE_PACK_IDS", "1") != "0"
+
+
+def pack_ids(segments) -> torch.Tensor:
+    """The flat int64 id vector of ``segments``, one after the other, in one
+    pass of the ``pack_ids`` HIP kernel (``csrc/pack_ids.hip``).
+
+    A segment is ``(src, h_out, expand, offset)``.  With ``expand`` None,
+    ``src`` holds ``rows * h_out`` ids and the segment is ``src + offset``.
+    With ``expand = (vocab, key_f)``, ``src`` holds one id per row and the
+    segment is that id's bag of ``h_out`` ids (:func:`multi_hot_expand`,
+    ``key_f`` from :func:`multi_hot_key`) ``+ offset``.  Every ``src`` is a
+    contiguous int64 tensor on one GPU.  More segments than one launch holds
+    (64) take several launches; empty segments are legal.
+    """
+    srcs, h_out, expand, vocab, key_f, offset = [], [], [], [], [], []
+    for src, h, exp, off in segments:
+        srcs.append(src)
+        h_out.append(int(h))
+        expand.append(exp is not None)
+        vocab.append(int(exp[0]) if exp is not None else 0)
+        key_f.append(to_int64(int(exp[1])) if exp is not None else 0)
+        offset.append(int(off))
+    return _backend.ops().pack_ids(srcs, h_out, expand, vocab, key_f, offset)
+
+
+def pack_ids_reference(segments) -> torch.Tensor:
+    """:func:`pack_ids` composed from the numpy expansion, ``torch.cat`` and
+    an add, on any device and never through the kernel: the definition the
+    kernel is tested against."""
+    parts = []
+    for src, h, exp, off in segments:
+        if exp is not None:
+            part = _multi_hot_expand_np(
+                src.reshape(-1), int(exp[0]), int(h),
+                int(exp[1])).to(src.device).reshape(-1)
+        else:
+            part = src.reshape(-1)
+        parts.append(part + int(off) if int(off) else part)
+    return torch.cat(parts)
+
+
 def _check_sr(sr, weight) -> None:
     if sr is None:
         return

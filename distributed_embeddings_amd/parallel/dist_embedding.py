@@ -32,7 +32,10 @@ import torch
 from torch import nn
 
 from ..layers.embedding import Embedding
+from ..ops import _backend
 from ..ops.embedding_lookup import (Ragged, embedding_lookup, mix64_int,
+                                    multi_hot_expand_keyed, multi_hot_key,
+                                    pack_ids, pack_ids_enabled,
                                     quantized_embedding_lookup, to_int64)
 from . import comm
 from .strategy import DistEmbeddingStrategy, TableConfig
@@ -124,6 +127,9 @@ class DistributedEmbedding(nn.Module):
     floating weight per id); every parallelism mode carries them to the
     lookup.  Weights are data here: a weights tensor that requires grad is
     rejected (a single-table :class:`Embedding` does give weight gradients).
+
+    Multi-hot expansion: after :meth:`set_multi_hot` a dense one-hot input is
+    expanded on the device into a bag of ids that its table's combiner sums.
     """
 
     def __init__(
@@ -160,6 +166,9 @@ class DistributedEmbedding(nn.Module):
         self._built = False
         self._local_batch = None
         self.quantized = False
+        self._mh_hotness = None  # set_multi_hot: hotness per input
+        self._mh_seed = 0
+        self._mh_pair = None     # per local pair: (h, vocab, key_f) or None
 
         plan = self.strategy
         # ---- data-parallel layers (replicated; grads allreduced) ----
@@ -336,6 +345,88 @@ class DistributedEmbedding(nn.Module):
         self.quantized = True
         return self
 
+    def set_multi_hot(self, hotness: Optional[Sequence[int]], seed: int = 0):
+        """Turns on-device multi-hot expansion on (``hotness``: one int >= 1
+        per input) or off (``None``).
+
+        With the mode on, the dense input of feature ``f`` is either one-hot,
+        ``[b]`` or ``[b, 1]``, and then expanded to ``hotness[f]`` ids per
+        sample by ``multi_hot_expand(ids, vocab, hotness[f], seed, feature=f)``
+        with ``vocab`` the table's full ``input_dim``; or it is
+        ``[b, hotness[f]]`` already and taken as it is.  ``Ragged`` inputs
+        pass through untouched.  ``hotness[f] > 1`` needs a table with a
+        combiner.  Table-parallel and column-sliced inputs cross the dp->mp
+        exchange one-hot and are expanded behind it, by the kernel that also
+        packs the fused group's ids; every other path expands and then runs
+        as it does for ``[b, h]`` inputs.  Either way the result equals
+        ``forward`` of the expanded ids, bit for bit.
+
+        ``hotness`` and ``seed`` are configuration, not checkpoint state: a
+        model has to be served with the seed (and hotness) it was trained
+        with, or its ids select other rows."""
+        plan = self.strategy
+        if hotness is None:
+            self._mh_hotness, self._mh_pair = None, None
+            return self
+        hotness = [int(h) for h in hotness]
+        if len(hotness) != len(plan.input_table_map):
+            raise ValueError(
+                f"hotness needs one entry per input: got {len(hotness)} for "
+                f"{len(plan.input_table_map)} inputs")
+        for f, h in enumerate(hotness):
+            if h < 1:
+                raise ValueError(f"hotness must be >= 1, got {h} (input {f})")
+            if h > 1 and plan.configs[plan.input_table_map[f]].combiner is None:
+                raise ValueError(
+                    f"input {f} has hotness {h} but its table has no "
+                    "combiner to reduce the bag")
+        self._mh_hotness = hotness
+        self._mh_seed = int(seed)
+        col_in = plan.input_groups[1]
+        self._mh_pair = [self._mh_spec(col_in[i])
+                         for i in plan.rank_input_ids[self.rank]]
+        return self
+
+    def extra_repr(self) -> str:
+        if self._mh_hotness is None:
+            return ""
+        return f"multi_hot={self._mh_hotness}, multi_hot_seed={self._mh_seed}"
+
+    def _mh_spec(self, f):
+        """(hotness, vocab, key_f) of input ``f``; None where nothing is
+        expanded (mode off, or hotness 1)."""
+        if self._mh_hotness is None or self._mh_hotness[f] == 1:
+            return None
+        plan = self.strategy
+        vocab = plan.configs[plan.input_table_map[f]].input_dim
+        return (self._mh_hotness[f], int(vocab),
+                multi_hot_key(self._mh_seed, f))
+
+    @staticmethod
+    def _mh_one_hot(x) -> bool:
+        return x.dim() == 1 or (x.dim() == 2 and x.shape[1] == 1)
+
+    def _mh_check_inputs(self, gids, inputs):
+        """With the mode on, a dense input is one-hot or [b, hotness]."""
+        if self._mh_hotness is None or len(gids) != len(inputs):
+            return
+        for f, x in zip(gids, inputs):
+            if isinstance(x, Ragged):
+                continue
+            h = self._mh_hotness[f]
+            if not (self._mh_one_hot(x)
+                    or (x.dim() == 2 and x.shape[1] == h)):
+                raise ValueError(
+                    f"input {f}: multi-hot mode takes dense ids of shape "
+                    f"[b], [b, 1] or [b, {h}], got {tuple(x.shape)}")
+
+    def _mh_expand(self, spec, x):
+        """``x`` expanded by ``spec`` when it is one-hot, else ``x``."""
+        if spec is None or isinstance(x, Ragged) or not self._mh_one_hot(x):
+            return x
+        h, vocab, key_f = spec
+        return multi_hot_expand_keyed(x.reshape(x.shape[0]), vocab, h, key_f)
+
     def _check_not_quantized(self, what):
         if self.quantized:
             raise RuntimeError(
@@ -395,10 +486,14 @@ class DistributedEmbedding(nn.Module):
                         f"Ragged.weights must hold one floating weight per "
                         f"id: got {x.weights.numel()} for "
                         f"{x.values.numel()} ids")
+        self._mh_check_inputs(
+            range(len(inputs)) if self.dp_input else self.local_input_ids(),
+            inputs)
         if self.dp_input:
             if len(inputs) != len(plan.input_table_map):
                 raise ValueError("wrong number of inputs")
-            dp_inputs = [inputs[i] for i in dp_in]
+            dp_inputs = [self._mh_expand(self._mh_spec(i), inputs[i])
+                         for i in dp_in]
             col_inputs = [inputs[i] for i in col_in]
             row_inputs = [inputs[i] for i in row_in]
         else:
@@ -414,7 +509,8 @@ class DistributedEmbedding(nn.Module):
             dp_out = [o.to(output_dtype) for o in dp_out]
         col_out = self._call_table_parallel(col_inputs, async_handle) \
             if (col_inputs or plan.col_table_ids) else []
-        row_out = self._call_row_slice(row_inputs) if row_inputs else []
+        row_out = self._call_row_slice(row_inputs, row_in) \
+            if row_inputs else []
 
         outs = dp_out + col_out + row_out
         return [outs[i] for i in plan.reverse_input_order]
@@ -771,12 +867,9 @@ class DistributedEmbedding(nn.Module):
                 # hotness-1 CSR gather: one cat + one cached-offset add for the
                 # whole group (instead of one add per pair per step).
                 metas = [(j, pair_ids[j].shape, pair_ids[j].numel()) for j in pair_js]
-                allids = _cat_or_view([pair_ids[j] for j in pair_js])
-                off_vec = self._offset_vector(gi, [(self._pair_row_offset[j], n)
-                                                   for j, _, n in metas],
-                                              allids.device)
-                if off_vec is not None:
-                    allids = allids + off_vec
+                allids = self._group_ids(
+                    gi, [(pair_ids[j], 1, None, self._pair_row_offset[j])
+                         for j in pair_js])
                 if offload:
                     allids_cpu = allids.cpu()
                     splits = torch.arange(allids_cpu.numel() + 1, dtype=torch.long)
@@ -800,6 +893,8 @@ class DistributedEmbedding(nn.Module):
                 # One CSR batch over all pairs of this group; splits merged on
                 # device (no host syncs even for ragged inputs).
                 val_parts, metas, row_offs = [], [], []
+                # per dense pair (hotness after expansion, expansion or None)
+                hots = {}
                 device = None
                 all_dense = all(not isinstance(pair_ids[j], Ragged) for j in pair_js)
                 for j in pair_js:
@@ -812,6 +907,14 @@ class DistributedEmbedding(nn.Module):
                     else:
                         nrows = ids.shape[0]
                         device = ids.device
+                        spec = self._mh_pair[j] if self._mh_pair else None
+                        if spec is not None and self._mh_one_hot(ids):
+                            hots[j] = (spec[0], spec)
+                        else:
+                            hots[j] = (ids.shape[1] if ids.dim() > 1 else 1,
+                                       None)
+                        if not all_dense:
+                            ids = self._mh_expand(hots[j][1], ids)
                         val_parts.append(ids)
                     row_offs.append((off, nrows))
                     metas.append((j, nrows))
@@ -823,12 +926,12 @@ class DistributedEmbedding(nn.Module):
                         if isinstance(ids, Ragged):
                             lp.append(ids.row_lengths())
                         else:
-                            h = ids.shape[1] if ids.dim() > 1 else 1
-                            lp.append(torch.full((ids.shape[0],), h,
+                            lp.append(torch.full((ids.shape[0],), hots[j][0],
                                                  dtype=torch.long, device=device))
                     return lp
 
-                allvals = _cat_or_view(val_parts)
+                if not all_dense:
+                    allvals = _cat_or_view(val_parts)
                 # per-id weights, only when a pair of the group has some:
                 # its unweighted pairs count with ones
                 allw = None
@@ -843,14 +946,21 @@ class DistributedEmbedding(nn.Module):
                         for j, v in zip(pair_js, val_parts)])
                 if all_dense:
                     # static shapes: per-element offsets + splits fully cached
-                    espec = []
-                    for j in pair_js:
-                        ids = pair_ids[j]
-                        h = ids.shape[1] if ids.dim() > 1 else 1
+                    espec, segs = [], []
+                    # an offloaded table expands on the host, in numpy
+                    on_host = offload and any(
+                        hots[j][1] is not None for j in pair_js)
+                    for j, ids in zip(pair_js, val_parts):
+                        h, spec = hots[j]
                         espec.append((self._pair_row_offset[j], ids.shape[0] * h))
-                    off_vec = self._offset_vector(gi, espec, device)
-                    if off_vec is not None:
-                        allvals = allvals + off_vec
+                        if on_host:
+                            ids = ids.cpu()
+                        if spec is None:
+                            segs.append((ids, 1, None, self._pair_row_offset[j]))
+                        else:
+                            segs.append((ids, h, spec[1:],
+                                         self._pair_row_offset[j]))
+                    allvals = self._group_ids(gi, segs)
                     skey = ("splits", gi, tuple(espec), str(device))
                     cache = getattr(self, "_off_cache", None) or {}
                     self._off_cache = cache
@@ -877,7 +987,7 @@ class DistributedEmbedding(nn.Module):
                         layer,
                         Ragged(allvals.cpu(), allsplits.cpu(),
                                None if allw is None else allw.cpu()),
-                        grp.combiner).to(allvals.device)
+                        grp.combiner).to(device)
                 else:
                     out = layer.csr_lookup(allvals, allsplits, grp.combiner,
                                            out_dtype=self._kernel_out_dtype(allvals),
@@ -890,6 +1000,33 @@ class DistributedEmbedding(nn.Module):
                 for (j, nrows), part in zip(metas, parts):
                     outs[j] = part
         return outs
+
+    def _group_ids(self, gi, segs):
+        """The flat id vector of one fused group from ``segs``, a list of
+        ``pack_ids`` segments ``(ids, h_out, expand, row offset)``.
+
+        One ``pack_ids`` launch when there is anything to do (an offset to
+        add or a bag to expand) and the kernel applies: contiguous int64 GPU
+        ids, the extension loaded, ``DE_PACK_IDS`` not 0.  Otherwise the torch
+        composition: expansion, cat (a view when the parts are adjacent),
+        cached offset vector add."""
+        if any(off or exp is not None for _, _, exp, off in segs) \
+                and pack_ids_enabled() and _backend.available() \
+                and all(ids.is_cuda and ids.dtype == torch.int64
+                        and ids.is_contiguous() for ids, _, _, _ in segs):
+            return pack_ids([(ids.reshape(-1), h, exp, off)
+                             for ids, h, exp, off in segs])
+        parts = [ids if exp is None
+                 else multi_hot_expand_keyed(ids.reshape(ids.shape[0]),
+                                             exp[0], h, exp[1])
+                 for ids, h, exp, _ in segs]
+        allids = _cat_or_view(parts)
+        off_vec = self._offset_vector(
+            gi, [(off, p.numel()) for p, (_, _, _, off) in zip(parts, segs)],
+            allids.device)
+        if off_vec is not None:
+            allids = allids + off_vec
+        return allids
 
     def _kernel_out_dtype(self, ids):
         """bf16 when the caller asked for bf16 outputs and the lookup runs
@@ -1110,7 +1247,9 @@ class DistributedEmbedding(nn.Module):
         buffer.  Packed rows are in worker order (see :meth:`packed_order`);
         the per-pair split + stack/merge copies of the general path
         disappear.  Requires :meth:`packed_forward_available` and hotness-1
-        dense inputs (or 2-D with a combiner).  (``DE_PACKED_SMAJ=1``
+        dense inputs (or 2-D with a combiner); in multi-hot mode
+        (:meth:`set_multi_hot`) the one-hot inputs are expanded like in
+        :meth:`forward`.  (``DE_PACKED_SMAJ=1``
         switches world==1 to a sample-major [b, P, width] layout — measured
         slower end-to-end, kept for experiments; hence the boolean in the
         return value.)
@@ -1120,6 +1259,7 @@ class DistributedEmbedding(nn.Module):
         self._output_dtype = output_dtype
         col_in = plan.input_groups[1]
         col_inputs = [inputs[i] for i in col_in]
+        self._mh_check_inputs(col_in, col_inputs)
         for j, x in enumerate(col_inputs):
             comb = plan.configs[plan.col_table_ids[plan.input_maps[1][j]]].combiner
             if isinstance(x, Ragged) or x.dim() > 2 or (
@@ -1144,6 +1284,9 @@ class DistributedEmbedding(nn.Module):
                 # but MEASURED SLOWER end-to-end: they destroy the lookup's
                 # per-table cache locality (pair-major streams each table's
                 # whole batch through one hot region).  Kept for measurement.
+                if self._mh_pair:
+                    pair_ids = [self._mh_expand(spec, ids) for spec, ids
+                                in zip(self._mh_pair, pair_ids)]
                 return self._packed_lookup_sample_major(pair_ids, b), True
             group_out = self._fused_group_lookup(pair_ids, unsplit=True)
             return group_out.view(len(pair_ids), b, -1), False
@@ -1200,7 +1343,7 @@ class DistributedEmbedding(nn.Module):
 
     # --------------------------------------------------------- row slice path
 
-    def _call_row_slice(self, row_inputs):
+    def _call_row_slice(self, row_inputs, row_gids):
         """Allgather ids -> offset local lookup (OOB->0) -> reduce-scatter.
 
         Parity: reference ``_call_row_slice`` (:889-904) with the xGMI-native
@@ -1230,6 +1373,9 @@ class DistributedEmbedding(nn.Module):
                 out = layer(g_ragged)                # [W*b, D]
             else:
                 gathered = comm.all_gather(x)        # [W*b, ...]
+                # multi-hot: expand behind the gather, with the full table's
+                # vocabulary, before the ids become shard-relative
+                gathered = self._mh_expand(self._mh_spec(row_gids[j]), gathered)
                 ids = gathered - shard.row_offset    # negative => OOB => zero row
                 out = layer(ids)                     # [W*b, (h,) D]
             outs.append(out.reshape(W, -1))

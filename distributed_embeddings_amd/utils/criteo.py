@@ -103,12 +103,16 @@ class SyntheticDLRMData:
                  device="cpu", rank: int = 0,
                  feature_ids: Optional[Sequence[int]] = None,
                  dp_input: bool = True, pool: int = 4, world: int = 1,
-                 learnable: bool = False):
+                 learnable: bool = False,
+                 multi_hot_sizes: Optional[Sequence[int]] = None):
         """``learnable=True`` makes labels a deterministic function of the
         first categorical feature (id parity), so a correctly-scaled
         optimizer drives the BCE well below the ln(2) random floor — the
         convergence smoke for the lr contract (random labels cannot
-        distinguish a working optimizer from a frozen one)."""
+        distinguish a working optimizer from a frozen one).
+
+        ``multi_hot_sizes`` (ids per sample, one int per table) makes every
+        categorical input ``[bs, h]`` random ids in place of ``[bs]``."""
         from .input_gen import make_batch
         self.num_batches = num_batches
         self.pool = []
@@ -118,11 +122,18 @@ class SyntheticDLRMData:
         for i in range(pool):
             g = torch.Generator().manual_seed(17 + 131 * rank + i)
             sizes = [table_sizes[t] for t in feature_ids]
-            cats = [c.to(device) for c in
-                    make_batch(sizes, [1] * len(sizes), bs, generator=g)]
+            if multi_hot_sizes is None:
+                cats = [c.to(device) for c in
+                        make_batch(sizes, [1] * len(sizes), bs, generator=g)]
+            else:
+                hot = [int(multi_hot_sizes[t]) for t in feature_ids]
+                cats = [c.to(device) for c in
+                        make_batch(sizes, hot, bs, generator=g,
+                                   keep_hot_dim=True)]
             num = torch.rand(local_bs, num_numerical, device=device)
             if learnable and cats:
-                labels = (cats[0][:local_bs] % 2).view(-1, 1).float()
+                first = cats[0][:local_bs].reshape(local_bs, -1)[:, 0]
+                labels = (first % 2).view(-1, 1).float()
             else:
                 labels = torch.randint(0, 2, (local_bs, 1), device=device).float()
             self.pool.append((num, cats, labels))

@@ -24,7 +24,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 
 import distributed_embeddings_amd as de
-from distributed_embeddings_amd.models.config import CRITEO_1TB_TABLE_SIZES
+from distributed_embeddings_amd.models.config import (CRITEO_1TB_TABLE_SIZES,
+                                                      MLPERF_MULTI_HOT_SIZES)
 from distributed_embeddings_amd.models.dlrm import DLRM
 from distributed_embeddings_amd.parallel.optim import SparseEmbeddingOptimizer
 from distributed_embeddings_amd.utils.criteo import RawBinaryDataset, SyntheticDLRMData
@@ -66,7 +67,32 @@ def parse_args():
                         "low-rank cross network (DLRM-DCNv2)")
     p.add_argument("--cross-layers", type=int, default=3)
     p.add_argument("--cross-rank", type=int, default=512)
+    p.add_argument("--multi-hot", default="none",
+                   help="none, mlperf (the benchmark model's 26 bag sizes, "
+                        "214 ids per sample) or a comma list with one bag "
+                        "size per table: the tables sum bags of that many ids")
+    p.add_argument("--multi-hot-source", choices=("expand", "data"),
+                   default="expand",
+                   help="expand: the one-hot ids of the dataset (or of the "
+                        "synthetic data) are expanded to bags on the device; "
+                        "data: synthetic [batch, h] ids (synthetic data only)")
+    p.add_argument("--multi-hot-seed", type=int, default=0,
+                   help="seed of the on-device expansion: serve a model with "
+                        "the seed it was trained with")
     return p.parse_args()
+
+
+def parse_multi_hot(spec: str, num_tables: int):
+    if spec == "none":
+        return None
+    if spec == "mlperf":
+        sizes = list(MLPERF_MULTI_HOT_SIZES)
+    else:
+        sizes = [int(v) for v in spec.split(",")]
+    if len(sizes) != num_tables:
+        raise SystemExit(f"--multi-hot needs {num_tables} sizes, "
+                         f"got {len(sizes)}")
+    return sizes
 
 
 def auc(scores: torch.Tensor, labels: torch.Tensor) -> float:
@@ -112,11 +138,17 @@ def main():
     table_sizes = CRITEO_1TB_TABLE_SIZES
     if args.table_size_cap:
         table_sizes = [min(s, args.table_size_cap) for s in table_sizes]
+    multi_hot = parse_multi_hot(args.multi_hot, len(table_sizes))
+    if multi_hot and args.multi_hot_source == "data" and args.dataset_path:
+        raise SystemExit("--multi-hot-source data needs synthetic data: the "
+                         "Criteo files hold one-hot ids (use expand)")
     with torch.device(device):
         model = DLRM(table_sizes, embedding_dim=args.embedding_dim,
                      strategy=args.dist_strategy, dp_input=args.dp_input or world == 1,
                      interaction=args.interaction,
-                     cross_layers=args.cross_layers, cross_rank=args.cross_rank)
+                     cross_layers=args.cross_layers, cross_rank=args.cross_rank,
+                     multi_hot_sizes=multi_hot,
+                     multi_hot_seed=args.multi_hot_seed)
 
     local_bs = args.batch_size // world
     feature_ids = model.local_cat_feature_ids()
@@ -131,7 +163,9 @@ def main():
                                  device=device, rank=rank,
                                  feature_ids=feature_ids,
                                  dp_input=args.dp_input or world == 1,
-                                 learnable=args.learnable_labels)
+                                 learnable=args.learnable_labels,
+                                 multi_hot_sizes=multi_hot
+                                 if args.multi_hot_source == "data" else None)
 
     # loss below is sum(BCE)/global_batch and dp grads are SUMMED
     # (average=False), so each grad is already the global-batch mean —

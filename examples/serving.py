@@ -25,7 +25,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
 
-from distributed_embeddings_amd.models.config import CRITEO_1TB_TABLE_SIZES
+from distributed_embeddings_amd.models.config import (CRITEO_1TB_TABLE_SIZES,
+                                                      MLPERF_MULTI_HOT_SIZES)
 from distributed_embeddings_amd.models.dlrm import DLRM
 
 
@@ -45,6 +46,11 @@ def parse_args():
     p.add_argument("--table-size-cap", type=int, default=None)
     p.add_argument("--graph", action="store_true",
                    help="capture the scoring step in a hipGraph")
+    p.add_argument("--multi-hot", choices=("none", "mlperf"), default="none",
+                   help="mlperf: sum-combiner tables, the one-hot request ids "
+                        "expanded on the device to the benchmark model's bags")
+    p.add_argument("--multi-hot-seed", type=int, default=0,
+                   help="the seed the model was trained with")
     return p.parse_args()
 
 
@@ -62,7 +68,10 @@ def main():
         sizes = [min(s, args.table_size_cap) for s in sizes]
     tdt = torch.bfloat16 if args.table_dtype == "bf16" else torch.float32
     with torch.device(device):
-        model = DLRM(sizes, embedding_dim=128, table_dtype=tdt)
+        model = DLRM(sizes, embedding_dim=128, table_dtype=tdt,
+                     multi_hot_sizes=MLPERF_MULTI_HOT_SIZES
+                     if args.multi_hot == "mlperf" else None,
+                     multi_hot_seed=args.multi_hot_seed)
     model.eval()
     if args.weights:
         if os.path.isdir(args.weights):

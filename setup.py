@@ -23,6 +23,7 @@ ext = CUDAExtension(
         "distributed_embeddings_amd/csrc/mlp_ops.hip",
         "distributed_embeddings_amd/csrc/cross_ops.hip",
         "distributed_embeddings_amd/csrc/wgrad_splitk.hip",
+        "distributed_embeddings_amd/csrc/pack_ids.hip",
     ],
     extra_compile_args={
         "cxx": ["-O3", "-std=c++17"],
