@@ -1044,6 +1044,130 @@ torch::Tensor dot_interact_bwd(torch::Tensor gout, torch::Tensor feats) {
   return gfeats;
 }
 
+// Narrow widths (D = 8, 16, 24; F <= 32): bindings of their own, so that the
+// four above keep rejecting these shapes.  The kernels move every feature row
+// as 16-B vectors, so the feature tensors must start on a 16-B boundary (rows
+// of 16, 32 or 48 bytes then do too); out / gout rows are 2-byte aligned.
+// As for the siblings, perm must be a permutation of [0, P): the backward
+// writes the rows of gpacked that perm names and leaves any other as
+// allocated.
+static void check_dot_interact_narrow_shape(int64_t F, int64_t D) {
+  TORCH_CHECK((D == 8 || D == 16 || D == 24) && F >= 1 && F <= 32,
+              "D in {8, 16, 24} and 1 <= F <= 32 required (got F=", F,
+              ", D=", D, ")");
+}
+
+static void check_align16(const torch::Tensor& t, const char* name) {
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, name,
+              " must be 16-byte aligned");
+}
+
+torch::Tensor dot_interact_narrow_fwd(torch::Tensor feats, int64_t out_w) {
+  CHECK_CUDA(feats); CHECK_CONTIG(feats);
+  TORCH_CHECK(feats.dtype() == torch::kBFloat16, "feats must be bf16");
+  TORCH_CHECK(feats.dim() == 3, "feats must be [B, F, D]");
+  const int64_t B = feats.size(0);
+  check_dot_interact_narrow_shape(feats.size(1), feats.size(2));
+  check_align16(feats, "feats");
+  const int F = (int)feats.size(1), D = (int)feats.size(2);
+  const int tri_n = F * (F - 1) / 2;
+  TORCH_CHECK(out_w >= tri_n + D, "out width too small");
+  auto out = torch::empty({B, out_w}, feats.options());
+  launch_dot_interact_fwd_narrow(feats.data_ptr(), out.data_ptr(), B, F, D,
+                                 (int)out_w, tri_n, current_stream());
+  return out;
+}
+
+torch::Tensor dot_interact_narrow_bwd(torch::Tensor gout, torch::Tensor feats) {
+  CHECK_CUDA(gout); CHECK_CUDA(feats);
+  CHECK_CONTIG(gout); CHECK_CONTIG(feats);
+  TORCH_CHECK(gout.dtype() == torch::kBFloat16 &&
+              feats.dtype() == torch::kBFloat16, "bf16 required");
+  TORCH_CHECK(gout.dim() == 2 && feats.dim() == 3,
+              "gout [B,W], feats [B,F,D]");
+  const int64_t B = feats.size(0);
+  check_dot_interact_narrow_shape(feats.size(1), feats.size(2));
+  check_align16(feats, "feats");
+  const int F = (int)feats.size(1), D = (int)feats.size(2);
+  const int tri_n = F * (F - 1) / 2;
+  TORCH_CHECK(gout.size(0) == B && gout.size(1) >= tri_n + D,
+              "gout must be [B, >= F(F-1)/2 + D]");
+  auto gfeats = torch::empty_like(feats);
+  launch_dot_interact_bwd_narrow(gout.data_ptr(), feats.data_ptr(),
+                                 gfeats.data_ptr(), B, F, D, (int)gout.size(1),
+                                 tri_n, current_stream());
+  return gfeats;
+}
+
+torch::Tensor dot_interact_narrow_fwd_packed(torch::Tensor bottom,
+                                             torch::Tensor packed,
+                                             torch::Tensor perm, int64_t out_w,
+                                             bool sample_major) {
+  CHECK_CUDA(bottom); CHECK_CUDA(packed); CHECK_CUDA(perm);
+  CHECK_CONTIG(bottom); CHECK_CONTIG(packed); CHECK_CONTIG(perm);
+  TORCH_CHECK(bottom.dtype() == torch::kBFloat16 &&
+              packed.dtype() == torch::kBFloat16, "bf16 required");
+  TORCH_CHECK(perm.dtype() == torch::kInt32, "perm must be int32");
+  TORCH_CHECK(bottom.dim() == 2 && packed.dim() == 3, "bottom [B,D], packed 3-D");
+  const int64_t B = bottom.size(0);
+  const int D = (int)bottom.size(1);
+  const int P = (int)(sample_major ? packed.size(1) : packed.size(0));
+  TORCH_CHECK(packed.size(sample_major ? 0 : 1) == B && packed.size(2) == D,
+              "shape mismatch");
+  TORCH_CHECK(perm.numel() == P, "perm must have P entries");
+  check_dot_interact_narrow_shape((int64_t)P + 1, bottom.size(1));
+  check_align16(bottom, "bottom");
+  check_align16(packed, "packed");
+  const int F = P + 1;
+  const int tri_n = F * (F - 1) / 2;
+  TORCH_CHECK(out_w >= tri_n + D, "out width too small");
+  const int64_t sb = sample_major ? P : 1;
+  const int64_t sp = sample_major ? 1 : B;
+  auto out = torch::empty({B, out_w}, bottom.options());
+  launch_dot_interact_fwd_narrow_packed(
+      bottom.data_ptr(), packed.data_ptr(), perm.data_ptr<int>(),
+      out.data_ptr(), B, F, D, (int)out_w, tri_n, sb, sp, current_stream());
+  return out;
+}
+
+std::vector<torch::Tensor> dot_interact_narrow_bwd_packed(torch::Tensor gout,
+                                                          torch::Tensor bottom,
+                                                          torch::Tensor packed,
+                                                          torch::Tensor perm,
+                                                          bool sample_major) {
+  CHECK_CUDA(gout); CHECK_CUDA(bottom); CHECK_CUDA(packed); CHECK_CUDA(perm);
+  CHECK_CONTIG(gout); CHECK_CONTIG(bottom); CHECK_CONTIG(packed);
+  CHECK_CONTIG(perm);
+  TORCH_CHECK(gout.dtype() == torch::kBFloat16 &&
+              bottom.dtype() == torch::kBFloat16 &&
+              packed.dtype() == torch::kBFloat16, "bf16 required");
+  TORCH_CHECK(perm.dtype() == torch::kInt32, "perm must be int32");
+  TORCH_CHECK(gout.dim() == 2 && bottom.dim() == 2 && packed.dim() == 3,
+              "gout [B,W], bottom [B,D], packed 3-D");
+  const int64_t B = bottom.size(0);
+  const int D = (int)bottom.size(1);
+  const int P = (int)(sample_major ? packed.size(1) : packed.size(0));
+  TORCH_CHECK(perm.numel() == P, "perm must have P entries");
+  TORCH_CHECK(packed.size(sample_major ? 0 : 1) == B && packed.size(2) == D,
+              "shape mismatch");
+  check_dot_interact_narrow_shape((int64_t)P + 1, bottom.size(1));
+  check_align16(bottom, "bottom");
+  check_align16(packed, "packed");
+  const int F = P + 1;
+  const int tri_n = F * (F - 1) / 2;
+  TORCH_CHECK(gout.size(0) == B && gout.size(1) >= tri_n + D,
+              "gout must be [B, >= F(F-1)/2 + D]");
+  const int64_t sb = sample_major ? P : 1;
+  const int64_t sp = sample_major ? 1 : B;
+  auto gbottom = torch::empty_like(bottom);
+  auto gpacked = torch::empty_like(packed);
+  launch_dot_interact_bwd_narrow_packed(
+      gout.data_ptr(), bottom.data_ptr(), packed.data_ptr(),
+      perm.data_ptr<int>(), gbottom.data_ptr(), gpacked.data_ptr(), B, F, D,
+      (int)gout.size(1), tri_n, sb, sp, current_stream());
+  return {gbottom, gpacked};
+}
+
 // ReLU backward fused with the bias gradient: one pass over grad_out and y
 // (mlp_ops.hip).  Outputs and the fp32 partial slab come from the torch
 // allocator, so the op can be captured in a hipGraph.
@@ -1334,6 +1458,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "fused DLRM pairwise-dot interaction forward (MFMA bf16, gfx950)");
   m.def("dot_interact_bwd", &dot_interact_bwd,
         "fused DLRM pairwise-dot interaction backward (MFMA bf16, gfx950)");
+  m.def("dot_interact_narrow_fwd", &dot_interact_narrow_fwd,
+        "interaction forward, D in {8, 16, 24}, F <= 32 (MFMA bf16, gfx950)");
+  m.def("dot_interact_narrow_bwd", &dot_interact_narrow_bwd,
+        "interaction backward, D in {8, 16, 24}, F <= 32 (MFMA bf16, gfx950)");
+  m.def("dot_interact_narrow_fwd_packed", &dot_interact_narrow_fwd_packed,
+        "narrow interaction on (bottom, packed, perm) (MFMA, gfx950)");
+  m.def("dot_interact_narrow_bwd_packed", &dot_interact_narrow_bwd_packed,
+        "narrow packed interaction backward -> (gbottom, gpacked) (gfx950)");
   m.def("relu_bwd_bias_grad", &relu_bwd_bias_grad,
         "ReLU backward + bias gradient in one pass -> (grad_in, bias_grad) "
         "(gfx950)");

@@ -12,7 +12,8 @@
 // 33 <= F <= 64 takes the 64-row kernels at the end of this file: a 4x4 grid
 // of 16x16 tiles, 10 of them on or below the diagonal.
 // Requirements: bf16 inputs, D % 32 == 0, and F <= 32, or F <= 64 with
-// D <= 256.
+// D <= 256.  D = 8, 16, 24 with F <= 32 takes the narrow kernels at the end of
+// this file: one v_mfma_f32_32x32x16_bf16 straight from global memory.
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
@@ -1553,4 +1554,396 @@ void launch_dot_interact_bwd64(const void* gout, const void* feats,
                      (const __hip_bfloat16*)gout,
                      (const __hip_bfloat16*)feats, (__hip_bfloat16*)gfeats, B,
                      F, D, out_w, tri_n);
+}
+
+// ---------------------------------------------------------------------------
+// Narrow widths: D = 8, 16, 24 with F <= 32.  The kernels above pad nothing:
+// they need D % 32 == 0 and are left as they are.
+//
+// A sample is at most 32 rows of 16, 32 or 48 bytes, so the whole feature
+// block is one (D = 24: two) 16-B chunk per lane, and with
+// v_mfma_f32_32x32x16_bf16 that chunk is already an operand:
+//   A: lane l supplies row l % 32,    k = 8 * (l / 32) .. + 7
+//   B: lane l supplies column l % 32, the same k
+//   C: register r of lane l is row 8 * (r / 4) + 4 * (l / 32) + r % 4,
+//      column l % 32
+// For the Gram matrix X X^T rows and columns are both features and k is d:
+// lane l loads chunk l / 32 of feature l % 32 from global memory and passes
+// the register as A and as B.  D = 8 has zeros in lanes >= 32; D = 24 runs a
+// second MFMA on chunk 2 (lanes < 32, zeros in the rest).  Lanes of features
+// >= F hold zeros; EXEC is all ones at every MFMA (the branches around them
+// are on wave-uniform values).
+//
+// One kernel per width serves the three layouts through a per-lane row
+// address: feature 0 is bottom + b * bstride, feature f >= 1 is
+// packed + (perm[f - 1] * sp + b * sb) * D.  The stacked [B, F, D] layout is
+// bottom = packed = feats, bstride = F * D, sb = F, sp = 1 and no perm (row f).
+// A perm entry outside [0, P) makes its feature a row of zeros whose gradient
+// is not written: no address is formed from it.
+//
+// A wave takes U consecutive samples at a time, all their loads in flight
+// ahead of the first MFMA (in the feature-major layout the U samples' rows are
+// adjacent, U * 2 * D bytes per feature), and strides over the batch.  Waves
+// share nothing: no block-level barrier.
+// ---------------------------------------------------------------------------
+
+typedef __attribute__((ext_vector_type(16))) float f32x16;
+
+#define DIN_WPB 4  // waves per block
+#define DIN_U_FWD 4
+#define DIN_U_BWD 2
+
+// Lane's feature row: element offset in sample 0 and per-sample stride.
+struct NarrowRow {
+  int64_t off, stride;
+  bool first;  // feature 0: bottom / gbottom
+  bool ok;     // f < F and the perm entry is a row of packed
+
+  __device__ __forceinline__ NarrowRow(const int* __restrict__ perm, int f,
+                                       int F, int D, int64_t bstride,
+                                       int64_t sb, int64_t sp) {
+    first = f == 0;
+    ok = f < F;
+    int p = f;
+    if (perm != nullptr && f >= 1 && f < F) {
+      p = perm[f - 1];
+      ok = (unsigned)p < (unsigned)(F - 1);
+    }
+    off = first ? 0 : (int64_t)p * sp * D;
+    stride = first ? bstride : sb * D;
+  }
+};
+
+template <int D, int U>
+__global__ __launch_bounds__(DIN_WPB* WAVE) void dot_interact_fwd_narrow(
+    const short* __restrict__ bottom, const short* __restrict__ packed,
+    const int* __restrict__ perm, short* __restrict__ out, int64_t B, int F,
+    int out_w, int tri_n, int64_t bstride, int64_t sb, int64_t sp) {
+  // per wave: the output row [tril | bottom | 0 up to a multiple of 8],
+  // <= 496 + 24 elements
+  constexpr int STAGE = 528;
+  __shared__ __attribute__((aligned(16))) short lds_all[DIN_WPB * STAGE];
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int lane = threadIdx.x & (WAVE - 1);
+  short* stage = lds_all + wave * STAGE;
+  const int f = lane & 31, h = lane >> 5;
+  const NarrowRow row(perm, f, F, D, bstride, sb, sp);
+  const bool ok0 = row.ok && h * 8 < D;   // chunk h
+  const bool ok2 = row.ok && D == 24 && h == 0;  // chunk 2
+  const short* src = (row.first ? bottom : packed) + row.off + h * 8;
+  const int width = tri_n + D;
+  const int width8 = (width + 7) & ~7;
+  const int nfull = out_w >> 3;  // whole 16-B chunks of the row
+  const int64_t groups = (B + U - 1) / U;
+  const int64_t n_waves = (int64_t)gridDim.x * DIN_WPB;
+
+  for (int64_t g = (int64_t)blockIdx.x * DIN_WPB + wave; g < groups;
+       g += n_waves) {
+    const int64_t b0 = g * U;
+    const bf16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
+    bf16x8 v[U], v2[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      v[u] = z;
+      v2[u] = z;
+      const int64_t b = b0 + u;
+      if (b < B && ok0) {
+        v[u] = *reinterpret_cast<const bf16x8*>(src + b * row.stride);
+      }
+      if (D == 24 && b < B && ok2) {
+        v2[u] = *reinterpret_cast<const bf16x8*>(src + b * row.stride + 16);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int64_t b = b0 + u;
+      if (b >= B) break;  // wave-uniform
+      f32x16 acc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f,
+                    0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(v[u], v[u], acc, 0, 0, 0);
+      if (D == 24) {
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(v2[u], v2[u], acc, 0, 0,
+                                                      0);
+      }
+      // strictly-lower elements into the row image: column f, 16 rows
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int i = 8 * (r >> 2) + 4 * h + (r & 3);
+        if (i > f && i < F) {
+          stage[i * (i - 1) / 2 + f] = f32_to_bf16_bits(acc[r]);
+        }
+      }
+      // bottom: the chunks that feature 0's lanes hold, bit for bit
+      if (f == 0) {
+        if (h * 8 < D) {
+#pragma unroll
+          for (int e = 0; e < 8; ++e) stage[tri_n + h * 8 + e] = v[u][e];
+        }
+        if (D == 24 && h == 0) {
+#pragma unroll
+          for (int e = 0; e < 8; ++e) stage[tri_n + 16 + e] = v2[u][e];
+        }
+      }
+      if (width + lane < width8) stage[width + lane] = 0;
+      wave_lds_fence();
+
+      short* orow = out + b * (int64_t)out_w;
+      for (int c = lane; c < nfull; c += WAVE) {
+        bf16x8 o = z;
+        if (c * 8 < width8) o = *reinterpret_cast<const bf16x8*>(&stage[c * 8]);
+        *reinterpret_cast<bf16x8_u*>(&orow[c * 8]) = o;
+      }
+      const int e = nfull * 8 + lane;  // the row's last out_w % 8 elements
+      if (e < out_w) orow[e] = e < width ? stage[e] : (short)0;
+      wave_lds_fence();  // the next sample overwrites the image
+    }
+  }
+}
+
+// Backward, the transposed product of dot_interact_bwd_packed on a narrow
+// image: gfeats^T[d][i] = sum_k X[k][d] * G[k][i], v_mfma_f32_16x16x32_bf16,
+// two MFMAs (feature tiles 0-15, 16-31; the second skipped on a scalar branch
+// when F <= 16) per 16 values of d.  X goes from the lanes' registers into a
+// [32][DP] LDS image, DP = 16 (D = 8, 16) or 32 (D = 24), rows >= F and
+// columns >= D zero; ds_read_b64_tr_b16 reads it transposed.  G fragments are
+// gathered from the staged gout row, the bottom-concat gradient is the C
+// operand of feature 0's column, results replace X in place as 8-B stores, and
+// every lane stores the chunk it loaded.
+//
+// Bank mapping of the image.  A transposed read takes, per 32-lane half, rows
+// 8g .. 8g + 3 for two values of g, 32 bytes (16 columns) of each.  With plain
+// 32-B rows (DP = 16) rows 0-3 are bytes 0-127 and rows 8-11 bytes 256-383:
+// the same 32 of the 64 banks.  With 64-B rows (DP = 32) row q of either block
+// starts on bank 16 q.  So every block of 8 rows is shifted by PAD more than
+// the one before, PAD = 128 bytes at DP = 16 and 32 bytes at DP = 32: the two
+// blocks of a half then land on disjoint banks (rows 0-3 on banks 0-31, rows
+// 8-11 on 32-63; or 8 banks each at 16 q and 16 q + 8).
+template <int D, int U>
+__global__ __launch_bounds__(DIN_WPB* WAVE) void dot_interact_bwd_narrow(
+    const short* __restrict__ gout, const short* __restrict__ bottom,
+    const short* __restrict__ packed, const int* __restrict__ perm,
+    short* gbottom, short* gpacked, int64_t B, int F, int out_w, int tri_n,
+    int64_t bstride, int64_t sb, int64_t sp) {
+  constexpr int DP = D == 24 ? 32 : 16;
+  constexpr int PAD = DP == 16 ? 64 : 16;  // elements
+  constexpr int XIMG = 32 * DP + 4 * PAD;
+  // gout row: tril chunks at [0, 496 + 7), the bottom part again at
+  // [512, 512 + D)
+  constexpr int PER_WAVE = XIMG + 512 + 32;
+  constexpr int NJ = DP / 16;
+  static_assert(PER_WAVE % 8 == 0, "16-B aligned per-wave regions");
+  __shared__ __attribute__((aligned(16))) short lds_all[DIN_WPB * PER_WAVE];
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int lane = threadIdx.x & (WAVE - 1);
+  short* x = lds_all + wave * PER_WAVE;
+  short* stage = x + XIMG;
+  short* gb = stage + 512;
+#define DIN_XOFF(row, col) ((row) * DP + ((row) >> 3) * PAD + (col))
+  const int f = lane & 31, h = lane >> 5;
+  const NarrowRow row(perm, f, F, D, bstride, sb, sp);
+  const bool ok0 = row.ok && h * 8 < D;
+  const bool ok2 = row.ok && D == 24 && h == 0;
+  const int64_t at = row.off + h * 8;
+  const short* src = (row.first ? bottom : packed) + at;
+  short* dst = (row.first ? gbottom : gpacked) + at;
+  const int r16 = lane & 15, khalf = lane >> 4;
+  const int64_t groups = (B + U - 1) / U;
+  const int64_t n_waves = (int64_t)gridDim.x * DIN_WPB;
+
+  for (int64_t g = (int64_t)blockIdx.x * DIN_WPB + wave; g < groups;
+       g += n_waves) {
+    const int64_t b0 = g * U;
+    const bf16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
+    bf16x8 v[U], v2[U], vt[U], vb[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      v[u] = z;
+      v2[u] = z;
+      vt[u] = z;
+      vb[u] = z;
+      const int64_t b = b0 + u;
+      if (b < B) {
+        // a tril chunk may run up to 7 elements into the bottom part, never
+        // past the row: D >= 8
+        const short* grow = gout + b * (int64_t)out_w;
+        if (lane * 8 < tri_n) {
+          vt[u] = *reinterpret_cast<const bf16x8_u*>(&grow[lane * 8]);
+        }
+        if (lane < D / 8) {
+          vb[u] = *reinterpret_cast<const bf16x8_u*>(&grow[tri_n + lane * 8]);
+        }
+        if (ok0) v[u] = *reinterpret_cast<const bf16x8*>(src + b * row.stride);
+        if (D == 24 && ok2) {
+          v2[u] = *reinterpret_cast<const bf16x8*>(src + b * row.stride + 16);
+        }
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int64_t b = b0 + u;
+      if (b >= B) break;  // wave-uniform
+      // every lane writes: zeros where it loaded nothing
+      *reinterpret_cast<bf16x8*>(&x[DIN_XOFF(f, h * 8)]) = v[u];
+      if (DP == 32) {
+        *reinterpret_cast<bf16x8*>(&x[DIN_XOFF(f, 16 + h * 8)]) = v2[u];
+      }
+      if (lane * 8 < tri_n) *reinterpret_cast<bf16x8*>(&stage[lane * 8]) = vt[u];
+      if (lane < 4) *reinterpret_cast<bf16x8*>(&gb[lane * 8]) = vb[u];
+      wave_lds_fence();
+
+      // B operand G[k][i] = G[i][k]: i = ni * 16 + r16, k = khalf * 8 + j
+      bf16x8 gf[2] = {z, z};
+#pragma unroll
+      for (int ni = 0; ni < 2; ++ni) {
+        if (ni == 0 || F > 16) {  // wave-uniform
+#pragma unroll
+          for (int j = 0; j < 8; ++j) {
+            const int i = ni * 16 + r16, k = khalf * 8 + j;
+            const bool ok = i < F && k < F && i != k;
+            const int r = i > k ? i : k, c = i > k ? k : i;
+            const short s = stage[ok ? r * (r - 1) / 2 + c : 0];
+            gf[ni][j] = ok ? s : (short)0;
+          }
+        }
+      }
+      // A operand X^T: the 16-lane group khalf takes rows 8 khalf .. + 3 and
+      // + 4 .. + 7 of columns d0 .. d0 + 15; lane 4q + p of the group supplies
+      // row q, columns 4p .. 4p + 3
+      const int xrow = khalf * 8 + (r16 >> 2), xcol = (lane & 3) * 4;
+      bf16x8 a[NJ];
+      bf16x4 gbv[NJ];
+#pragma unroll
+      for (int t = 0; t < NJ; ++t) {
+        const int d0 = t * 16;
+        const v4i16_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+            (lds_v4i16_t*)(x + DIN_XOFF(xrow, d0 + xcol)));
+        const v4i16_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+            (lds_v4i16_t*)(x + DIN_XOFF(xrow + 4, d0 + xcol)));
+        a[t] = bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+        gbv[t] = *reinterpret_cast<const bf16x4*>(&gb[d0 + khalf * 4]);
+      }
+      wave_lds_fence();  // results replace X from here on
+#pragma unroll
+      for (int t = 0; t < NJ; ++t) {
+        const int d0 = t * 16;
+        // bottom-concat gradient of feature 0: the C operand of its column
+        f32x4 c0 = {0.f, 0.f, 0.f, 0.f};
+        if (r16 == 0 && d0 + khalf * 4 < D) {
+#pragma unroll
+          for (int reg = 0; reg < 4; ++reg) {
+            c0[reg] = bf16_bits_to_f32(gbv[t][reg]);
+          }
+        }
+        const f32x4 acc0 =
+            __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[t], gf[0], c0, 0, 0, 0);
+        const bf16x4 o0 = {
+            f32_to_bf16_bits(acc0[0]), f32_to_bf16_bits(acc0[1]),
+            f32_to_bf16_bits(acc0[2]), f32_to_bf16_bits(acc0[3])};
+        *reinterpret_cast<bf16x4*>(&x[DIN_XOFF(r16, d0 + khalf * 4)]) = o0;
+        if (F > 16) {  // wave-uniform; rows >= F are never stored
+          const f32x4 zc = {0.f, 0.f, 0.f, 0.f};
+          const f32x4 acc1 =
+              __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[t], gf[1], zc, 0, 0, 0);
+          const bf16x4 o1 = {
+              f32_to_bf16_bits(acc1[0]), f32_to_bf16_bits(acc1[1]),
+              f32_to_bf16_bits(acc1[2]), f32_to_bf16_bits(acc1[3])};
+          *reinterpret_cast<bf16x4*>(&x[DIN_XOFF(16 + r16, d0 + khalf * 4)]) =
+              o1;
+        }
+      }
+      wave_lds_fence();
+
+      // each lane stores the chunk(s) it loaded
+      const bf16x8 w = *reinterpret_cast<const bf16x8*>(&x[DIN_XOFF(f, h * 8)]);
+      if (ok0) *reinterpret_cast<bf16x8*>(dst + b * row.stride) = w;
+      if (D == 24) {
+        const bf16x8 w2 =
+            *reinterpret_cast<const bf16x8*>(&x[DIN_XOFF(f, 16 + h * 8)]);
+        if (ok2) *reinterpret_cast<bf16x8*>(dst + b * row.stride + 16) = w2;
+      }
+      wave_lds_fence();  // the next sample overwrites the image
+    }
+  }
+#undef DIN_XOFF
+}
+
+static void din_check(int F, int D) {
+  if ((D != 8 && D != 16 && D != 24) || F < 1 || F > 32) {
+    throw std::invalid_argument(
+        "dot_interact narrow kernels: D in {8, 16, 24}, 1 <= F <= 32");
+  }
+}
+
+// one group of U samples per wave up to this many blocks, a stride beyond
+static int din_blocks(int64_t B, int U) {
+  const int64_t groups = (B + U - 1) / U;
+  const int64_t blocks = (groups + DIN_WPB - 1) / DIN_WPB;
+  return (int)(blocks < 4096 ? blocks : 4096);
+}
+
+static void din_launch_fwd(const void* bottom, const void* packed,
+                           const int* perm, void* out, int64_t B, int F, int D,
+                           int out_w, int tri_n, int64_t bstride, int64_t sb,
+                           int64_t sp, hipStream_t stream) {
+  din_check(F, D);
+  if (B == 0) return;
+  const int blocks = din_blocks(B, DIN_U_FWD);
+#define LFWD(DD)                                                              \
+  hipLaunchKernelGGL((dot_interact_fwd_narrow<DD, DIN_U_FWD>), dim3(blocks),  \
+                     dim3(DIN_WPB* WAVE), 0, stream, (const short*)bottom,    \
+                     (const short*)packed, perm, (short*)out, B, F, out_w,    \
+                     tri_n, bstride, sb, sp)
+  if (D == 8) { LFWD(8); } else if (D == 16) { LFWD(16); } else { LFWD(24); }
+#undef LFWD
+}
+
+static void din_launch_bwd(const void* gout, const void* bottom,
+                           const void* packed, const int* perm, void* gbottom,
+                           void* gpacked, int64_t B, int F, int D, int out_w,
+                           int tri_n, int64_t bstride, int64_t sb, int64_t sp,
+                           hipStream_t stream) {
+  din_check(F, D);
+  if (B == 0) return;
+  const int blocks = din_blocks(B, DIN_U_BWD);
+#define LBWD(DD)                                                              \
+  hipLaunchKernelGGL((dot_interact_bwd_narrow<DD, DIN_U_BWD>), dim3(blocks),  \
+                     dim3(DIN_WPB* WAVE), 0, stream, (const short*)gout,      \
+                     (const short*)bottom, (const short*)packed, perm,        \
+                     (short*)gbottom, (short*)gpacked, B, F, out_w, tri_n,    \
+                     bstride, sb, sp)
+  if (D == 8) { LBWD(8); } else if (D == 16) { LBWD(16); } else { LBWD(24); }
+#undef LBWD
+}
+
+void launch_dot_interact_fwd_narrow(const void* feats, void* out, int64_t B,
+                                    int F, int D, int out_w, int tri_n,
+                                    hipStream_t stream) {
+  din_launch_fwd(feats, feats, nullptr, out, B, F, D, out_w, tri_n,
+                 (int64_t)F * D, F, 1, stream);
+}
+
+void launch_dot_interact_bwd_narrow(const void* gout, const void* feats,
+                                    void* gfeats, int64_t B, int F, int D,
+                                    int out_w, int tri_n, hipStream_t stream) {
+  din_launch_bwd(gout, feats, feats, nullptr, gfeats, gfeats, B, F, D, out_w,
+                 tri_n, (int64_t)F * D, F, 1, stream);
+}
+
+void launch_dot_interact_fwd_narrow_packed(const void* bottom,
+                                           const void* packed, const int* perm,
+                                           void* out, int64_t B, int F, int D,
+                                           int out_w, int tri_n, int64_t sb,
+                                           int64_t sp, hipStream_t stream) {
+  din_launch_fwd(bottom, packed, perm, out, B, F, D, out_w, tri_n, D, sb, sp,
+                 stream);
+}
+
+void launch_dot_interact_bwd_narrow_packed(const void* gout, const void* bottom,
+                                           const void* packed, const int* perm,
+                                           void* gbottom, void* gpacked,
+                                           int64_t B, int F, int D, int out_w,
+                                           int tri_n, int64_t sb, int64_t sp,
+                                           hipStream_t stream) {
+  din_launch_bwd(gout, bottom, packed, perm, gbottom, gpacked, B, F, D, out_w,
+                 tri_n, D, sb, sp, stream);
 }

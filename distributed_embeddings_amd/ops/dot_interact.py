@@ -5,9 +5,11 @@ Replaces the stack + bmm + tril-mask + concat chain of the reference
 (``csrc/dot_interact.hip``).  Falls back to plain torch ops off-GPU, for
 inputs that are not bf16, and for shapes the kernels do not take: they need
 D % 32 == 0 and either F <= 32, or F <= 64 with D <= 256 (F counts the
-bottom-MLP output as feature 0).
+bottom-MLP output as feature 0).  D = 8, 16 and 24 with F <= 32 run the narrow
+kernels (``narrow_shape_ok``); ``DE_DI_NARROW=0`` sends them to the torch ops.
 """
 
+import os
 from typing import List
 
 import torch
@@ -22,6 +24,22 @@ def kernel_shape_ok(f: int, d: int) -> bool:
     return f <= 32 or (f <= 64 and d <= 256)
 
 
+def narrow_shape_ok(f: int, d: int) -> bool:
+    """Whether the narrow-width HIP kernels take ``f`` features of width ``d``."""
+    return d in (8, 16, 24) and 1 <= f <= 32
+
+
+def _use_narrow(f: int, d: int) -> bool:
+    return narrow_shape_ok(f, d) and os.environ.get("DE_DI_NARROW", "1") != "0"
+
+
+def _aligned16(t: torch.Tensor) -> torch.Tensor:
+    """Contiguous ``t`` on a 16-byte boundary, as the narrow kernels' vector
+    loads need: a view at an odd storage offset is copied."""
+    t = t.contiguous()
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
 class _DotInteract(torch.autograd.Function):
     @staticmethod
     def forward(ctx, feats, out_w):
@@ -32,6 +50,19 @@ class _DotInteract(torch.autograd.Function):
     def backward(ctx, gout):
         (feats,) = ctx.saved_tensors
         gfeats = _backend.ops().dot_interact_bwd(gout.contiguous(), feats)
+        return gfeats, None
+
+
+class _DotInteractNarrow(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, feats, out_w):
+        ctx.save_for_backward(feats)
+        return _backend.ops().dot_interact_narrow_fwd(feats, out_w)
+
+    @staticmethod
+    def backward(ctx, gout):
+        (feats,) = ctx.saved_tensors
+        gfeats = _backend.ops().dot_interact_narrow_bwd(gout.contiguous(), feats)
         return gfeats, None
 
 
@@ -64,6 +95,22 @@ class _DotInteractPacked(torch.autograd.Function):
         return gbottom, gpacked, None, None, None
 
 
+class _DotInteractNarrowPacked(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, bottom, packed, perm, out_w, sample_major):
+        ctx.save_for_backward(bottom, packed, perm)
+        ctx.sample_major = sample_major
+        return _backend.ops().dot_interact_narrow_fwd_packed(
+            bottom, packed, perm, out_w, sample_major)
+
+    @staticmethod
+    def backward(ctx, gout):
+        bottom, packed, perm = ctx.saved_tensors
+        gbottom, gpacked = _backend.ops().dot_interact_narrow_bwd_packed(
+            gout.contiguous(), bottom, packed, perm, ctx.sample_major)
+        return gbottom, gpacked, None, None, None
+
+
 def dot_interact_packed(packed: torch.Tensor, bottom_mlp_out: torch.Tensor,
                         perm: torch.Tensor, pad_to: int = 0,
                         sample_major: bool = False) -> torch.Tensor:
@@ -83,11 +130,15 @@ def dot_interact_packed(packed: torch.Tensor, bottom_mlp_out: torch.Tensor,
     width = f * (f - 1) // 2 + d
     out_w = max(pad_to, width)
     if (packed.is_cuda and packed.dtype == torch.bfloat16
-            and bottom_mlp_out.dtype == torch.bfloat16
-            and kernel_shape_ok(f, d)):
-        return _DotInteractPacked.apply(bottom_mlp_out.contiguous(),
-                                        packed.contiguous(), perm, out_w,
-                                        sample_major)
+            and bottom_mlp_out.dtype == torch.bfloat16):
+        if kernel_shape_ok(f, d):
+            return _DotInteractPacked.apply(bottom_mlp_out.contiguous(),
+                                            packed.contiguous(), perm, out_w,
+                                            sample_major)
+        if _use_narrow(f, d):
+            return _DotInteractNarrowPacked.apply(
+                _aligned16(bottom_mlp_out), _aligned16(packed), perm, out_w,
+                sample_major)
     # fallback (CPU / unsupported shapes): materialize [B, F, D] and reuse
     # the plain path
     sel = packed.index_select(1, perm.long()) if sample_major else \
@@ -103,7 +154,9 @@ def dot_interact(emb_outs: List[torch.Tensor], bottom_mlp_out: torch.Tensor,
     f, d = feats.shape[1], feats.shape[2]
     width = f * (f - 1) // 2 + d
     out_w = max(pad_to, width)
-    if (feats.is_cuda and feats.dtype == torch.bfloat16
-            and kernel_shape_ok(f, d)):
-        return _DotInteract.apply(feats.contiguous(), out_w)
+    if feats.is_cuda and feats.dtype == torch.bfloat16:
+        if kernel_shape_ok(f, d):
+            return _DotInteract.apply(feats.contiguous(), out_w)
+        if _use_narrow(f, d):
+            return _DotInteractNarrow.apply(_aligned16(feats), out_w)
     return _torch_dot_interact(feats, out_w)

@@ -12,6 +12,8 @@ over rounds of the mean call time, taken with device events.
   python tools/bench_interact.py --only packed --rounds 1 --iters 3  # counter runs
   python tools/bench_interact.py --features 40 --only packed
   python tools/bench_interact.py --features 40 --only torch  # the torch fallback
+  python tools/bench_interact.py --dim 16 --only op   # the public op (narrow kernels)
+  DE_DI_NARROW=0 python tools/bench_interact.py --dim 16 --only op  # its fallback
 
 --ext times another build of the extension (e.g. the parent commit's) on the
 same inputs; run the two builds in alternating processes.
@@ -63,12 +65,17 @@ def sweep_wpb(argv, values):
         subprocess.run([sys.executable, __file__] + argv, env=e, check=True)
 
 
-def torch_runs(packed, bottom, perm, gout, out_w, sm, tag, gb_fwd, gb_bwd):
-    """The fallback of ops.dot_interact.dot_interact_packed, forward alone and
-    backward alone (autograd over a graph built once)."""
+def torch_runs(packed, bottom, perm, gout, out_w, sm, tag, gb_fwd, gb_bwd,
+               public_op=False):
+    """The fallback of ops.dot_interact.dot_interact_packed, or with
+    ``public_op`` the op itself wherever it routes the shape, forward alone
+    and backward alone (autograd over a graph built once)."""
     from distributed_embeddings_amd.ops import dot_interact as di
 
     def fwd(pk, bt):
+        if public_op:
+            return di.dot_interact_packed(pk, bt, perm, pad_to=out_w,
+                                          sample_major=sm)
         sel = pk.index_select(1, perm.long()) if sm else \
             pk.index_select(0, perm.long()).transpose(0, 1)
         feats = torch.cat([bt.unsqueeze(1), sel], dim=1)
@@ -82,9 +89,10 @@ def torch_runs(packed, bottom, perm, gout, out_w, sm, tag, gb_fwd, gb_bwd):
         with torch.no_grad():
             fwd(packed, bottom)
 
+    name = "op    " if public_op else "torch "
     return [
-        (f"fwd  torch  {tag}", gb_fwd, fwd_only),
-        (f"bwd  torch  {tag}", gb_bwd,
+        (f"fwd  {name} {tag}", gb_fwd, fwd_only),
+        (f"bwd  {name} {tag}", gb_bwd,
          lambda: torch.autograd.grad(out, (pk, bt), gout, retain_graph=True)),
     ]
 
@@ -92,12 +100,16 @@ def torch_runs(packed, bottom, perm, gout, out_w, sm, tag, gb_fwd, gb_bwd):
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--ext", default=None)
-    p.add_argument("--only", choices=("all", "packed", "torch"), default="all",
+    p.add_argument("--only", choices=("all", "packed", "torch", "op"),
+                   default="all",
                    help="torch: the ops' torch fallback on the packed input "
-                        "(what shapes outside the kernels' cap run)")
+                        "(what shapes outside the kernels' cap run); op: the "
+                        "public op under autograd, wherever it routes")
     p.add_argument("--features", type=int, default=27,
                    help="F, counting the bottom-MLP output")
-    p.add_argument("--width", type=int, default=128, help="D")
+    p.add_argument("--width", "--dim", type=int, default=128,
+                   help="D: a multiple of 32, or 8, 16, 24 (with --only op "
+                        "or torch: the raw packed bindings reject those)")
     p.add_argument("--sample-major", action="store_true",
                    help="packed block as [B, P, D] (the world==1 layout)")
     p.add_argument("--rounds", type=int, default=7)
@@ -122,10 +134,11 @@ def main():
     gout = torch.randn(B, out_w, device="cuda").bfloat16()
     tag = "samp-major" if sm else "feat-major"
     print(f"B={B} F={F} D={D} out_w={out_w}")
-    if args.only == "torch":
+    if args.only in ("torch", "op"):
         runs = torch_runs(packed, bottom, perm, gout, out_w, sm, tag,
-                          gb_fwd, gb_bwd)
-        print("ext: none (torch ops)")
+                          gb_fwd, gb_bwd, public_op=args.only == "op")
+        print("ext: none (torch ops)" if args.only == "torch" else
+              f"public op, DE_DI_NARROW={os.environ.get('DE_DI_NARROW', '1')}")
     else:
         ext = load_ext(args.ext)
         runs = [
