@@ -761,42 +761,68 @@ void sparse_row_update(torch::Tensor weight, torch::Tensor state,
                            current_stream());
 }
 
-void csr_fused_optimizer_apply(torch::Tensor weight, torch::Tensor state,
-                               torch::Tensor values, torch::Tensor row_splits,
-                               torch::Tensor grad_out, torch::Tensor lr,
-                               bool mean, bool adagrad, double eps,
-                               std::optional<torch::Tensor> per_id_w,
-                               std::optional<torch::Tensor> sr,
-                               std::optional<torch::Tensor> adam_step,
-                               double beta1, double beta2,
-                               bool deterministic) {
-  // adam_step (int64 [1] on the device) selects lazy Adam: state is
-  // [2, vocab, width], adagrad has to be false, and an apply that launches
-  // adds 1 to the step on the device.
-  // All-device sorted pipeline (no host sync; hipGraph-capturable):
-  // sort (id, pos) -> permute row-ids -> head-flag unique -> segment pad ->
-  // one direct update per unique row (long segments chunked with one atomic
-  // per partial, or, deterministic, one slab row per partial and a
-  // fixed-order combine).  Replaces both torch sparse grads and the naive
-  // atomic scatter (hot-row same-address chains).
-  CHECK_CUDA(weight); CHECK_CUDA(values); CHECK_CUDA(row_splits);
-  CHECK_CUDA(grad_out); CHECK_CUDA(lr);
-  CHECK_CONTIG(weight); CHECK_CONTIG(values); CHECK_CONTIG(row_splits);
-  CHECK_CONTIG(grad_out);
+// The id-only half of the fused update: build_sorted_segments with seg padded
+// (launch_pad_seg_offsets), plus the sizes the apply checks its arguments
+// against.  It depends on the ids, the row lengths and the per-id weights
+// alone, so it can be built as soon as the forward lookup is launched.  An
+// empty plan (no ids or no rows) holds no tensors and applies as a no-op.
+struct SortPlan {
+  SortedSegments ss;
+  int64_t nnz = 0;
+  int64_t num_rows = 0;
+  int64_t vocab = 0;
+  bool empty() const { return num_rows <= 0 || nnz <= 0; }
+};
+
+// All on the device, no host sync; the same kernels and sort dispatch
+// (DE_USE_ROCPRIM_SORT included) as the one-shot csr_fused_optimizer_apply.
+SortPlan csr_sort_plan(torch::Tensor values, torch::Tensor row_splits,
+                       int64_t vocab, bool mean,
+                       std::optional<torch::Tensor> per_id_w) {
+  CHECK_CUDA(values); CHECK_CUDA(row_splits);
+  CHECK_CONTIG(values); CHECK_CONTIG(row_splits);
+  TORCH_CHECK(vocab >= 0, "vocab must not be negative, got ", vocab);
+  const float* user_w = per_id_w_ptr(per_id_w, values);
+  SortPlan plan;
+  plan.nnz = values.numel();
+  plan.num_rows = row_splits.numel() - 1;
+  plan.vocab = vocab;
+  if (plan.empty()) return plan;
+  auto stream = current_stream();
+  plan.ss = build_sorted_segments(values, row_splits, vocab, mean, user_w,
+                                  stream);
+  launch_pad_seg_offsets(plan.ss.seg.data_ptr<int64_t>(), plan.nnz,
+                         plan.ss.num_unique.data_ptr<int32_t>(),
+                         plan.ss.bounds.data_ptr<int64_t>(), stream);
+  return plan;
+}
+
+// What the apply has checked about its arguments.
+struct FusedApplyArgs {
+  int64_t* sr_p;  // {seed, step} of stochastic rounding, or nullptr
+  bool rowwise;   // row-wise Adagrad state
+};
+
+// The one copy of the apply's argument checks; launches nothing.  nnz and
+// num_rows are the plan's (or, for the one-shot call, those of the ids the
+// plan will be built from): without ids or rows the apply is a no-op, and the
+// Adagrad state and the shape of grad_out are not looked at.
+static FusedApplyArgs check_fused_apply(
+    const torch::Tensor& weight, const torch::Tensor& state,
+    const torch::Tensor& grad_out, const torch::Tensor& lr, bool adagrad,
+    const std::optional<torch::Tensor>& sr,
+    const std::optional<torch::Tensor>& adam_step, double beta1, double beta2,
+    int64_t nnz, int64_t num_rows) {
+  CHECK_CUDA(weight); CHECK_CUDA(grad_out); CHECK_CUDA(lr);
+  CHECK_CONTIG(weight); CHECK_CONTIG(grad_out);
+  TORCH_CHECK(weight.dim() == 2, "weight must be [vocab, width]");
   TORCH_CHECK(weight.dtype() == torch::kFloat32 ||
               weight.dtype() == torch::kBFloat16);
   TORCH_CHECK((grad_out.dtype() == torch::kFloat32 ||
                grad_out.dtype() == torch::kBFloat16) &&
               lr.dtype() == torch::kFloat32);
-  const float* user_w = per_id_w_ptr(per_id_w, values);
-  int64_t* sr_p = sr_ptr(sr, weight);
-  const bool wbf16 = weight.dtype() == torch::kBFloat16;
-  const int64_t num_rows = row_splits.numel() - 1;
-  const int64_t nnz = values.numel();
-  const int64_t vocab = weight.size(0);
-  const int width = (int)weight.size(1);
-  const bool adam = adam_step.has_value();
-  if (adam) {
+  FusedApplyArgs args{sr_ptr(sr, weight), false};
+  if (adam_step.has_value()) {
     TORCH_CHECK(!adagrad, "adam_step and adagrad exclude each other");
     check_adam_state(state, weight, beta1, beta2);
     const torch::Tensor& t = *adam_step;
@@ -806,17 +832,36 @@ void csr_fused_optimizer_apply(torch::Tensor weight, torch::Tensor state,
     TORCH_CHECK(t.device() == weight.device(),
                 "adam_step must be on the weight's device");
   }
-  if (num_rows <= 0 || nnz <= 0) return;
+  if (num_rows <= 0 || nnz <= 0) return args;
+  // srow indexes rows of grad_out
+  TORCH_CHECK(grad_out.numel() == num_rows * weight.size(1),
+              "grad_out must be [num_rows, width] = [", num_rows, ", ",
+              weight.size(1), "], got ", grad_out.sizes());
+  if (adagrad) args.rowwise = check_adagrad_state(state, weight);
+  return args;
+}
+
+// The gradient half on checked arguments: one direct update per unique row of
+// the plan (long segments chunked with one atomic per partial, or,
+// deterministic, one slab row per partial and a fixed-order combine).
+static void apply_sort_plan(torch::Tensor weight, torch::Tensor state,
+                            const SortPlan& plan, torch::Tensor grad_out,
+                            torch::Tensor lr, bool adagrad, double eps,
+                            const FusedApplyArgs& args,
+                            std::optional<torch::Tensor> adam_step,
+                            double beta1, double beta2, bool deterministic) {
+  if (plan.empty()) return;
+  const SortedSegments& ss = plan.ss;
+  const bool wbf16 = weight.dtype() == torch::kBFloat16;
+  const int64_t nnz = plan.nnz;
+  const int64_t vocab = weight.size(0);
+  const int width = (int)weight.size(1);
+  const bool adam = adam_step.has_value();
   auto stream = current_stream();
-  auto i64 = values.options();
-  auto i32 = values.options().dtype(torch::kInt32);
+  auto i64 = ss.sorted_ids.options();
+  auto i32 = i64.dtype(torch::kInt32);
   auto f32 = grad_out.options().dtype(torch::kFloat32);
 
-  auto ss = build_sorted_segments(values, row_splits, vocab, mean, user_w,
-                                  stream);
-  launch_pad_seg_offsets(ss.seg.data_ptr<int64_t>(), nnz,
-                         ss.num_unique.data_ptr<int32_t>(),
-                         ss.bounds.data_ptr<int64_t>(), stream);
   auto long_rows = torch::empty({nnz}, i64);
   auto long_count = torch::empty({1}, i32);
   auto work_items = torch::empty({nnz / 64 + 64}, i64);
@@ -825,11 +870,7 @@ void csr_fused_optimizer_apply(torch::Tensor weight, torch::Tensor state,
   torch::Tensor scratch;
   float* scratch_ptr = nullptr;
   int64_t scratch_rows = 0;
-  bool rowwise = false;
-  if (adagrad) {
-    rowwise = check_adagrad_state(state, weight);
-    state_ptr = state.data_ptr<float>();
-  }
+  if (adagrad) state_ptr = state.data_ptr<float>();
   AdamConfig cfg{beta1, beta2, vocab, nullptr, nullptr};
   torch::Tensor a_t;
   if (adam) {
@@ -857,9 +898,60 @@ void csr_fused_optimizer_apply(torch::Tensor weight, torch::Tensor state,
                                  long_count.data_ptr<int32_t>(),
                                  work_items.data_ptr<int64_t>(),
                                  n_work.data_ptr<int32_t>(), scratch_ptr,
-                                 scratch_rows, adagrad, rowwise, sr_p,
-                                 adam ? &cfg : nullptr, det.slab_ptr(),
-                                 det.work_base_ptr(), stream);
+                                 scratch_rows, adagrad, args.rowwise,
+                                 args.sr_p, adam ? &cfg : nullptr,
+                                 det.slab_ptr(), det.work_base_ptr(), stream);
+}
+
+// The gradient half of the fused update on a csr_sort_plan.  Reads the plan's
+// tensors only and leaves them as they are, so one plan can be applied more
+// than once.  adam_step (int64 [1] on the device) selects lazy Adam: state is
+// [2, vocab, width], adagrad has to be false, and an apply that launches
+// adds 1 to the step on the device.
+void csr_fused_optimizer_apply_planned(torch::Tensor weight,
+                                       torch::Tensor state,
+                                       const SortPlan& plan,
+                                       torch::Tensor grad_out,
+                                       torch::Tensor lr, bool adagrad,
+                                       double eps,
+                                       std::optional<torch::Tensor> sr,
+                                       std::optional<torch::Tensor> adam_step,
+                                       double beta1, double beta2,
+                                       bool deterministic) {
+  const FusedApplyArgs args =
+      check_fused_apply(weight, state, grad_out, lr, adagrad, sr, adam_step,
+                        beta1, beta2, plan.nnz, plan.num_rows);
+  TORCH_CHECK(plan.vocab == weight.size(0),
+              "the sort plan was built for vocab ", plan.vocab,
+              ", the weight has ", weight.size(0), " rows");
+  TORCH_CHECK(plan.empty() || plan.ss.sorted_ids.device() == weight.device(),
+              "the sort plan must be on the weight's device");
+  apply_sort_plan(weight, state, plan, grad_out, lr, adagrad, eps, args,
+                  adam_step, beta1, beta2, deterministic);
+}
+
+// Plan and planned apply in one call: the all-device sorted pipeline (no host
+// sync; hipGraph-capturable) sort (id, pos) -> permute row-ids -> head-flag
+// unique -> segment pad -> update.  Replaces both torch sparse grads and the
+// naive atomic scatter (hot-row same-address chains).  Every argument is
+// checked before the first launch.
+void csr_fused_optimizer_apply(torch::Tensor weight, torch::Tensor state,
+                               torch::Tensor values, torch::Tensor row_splits,
+                               torch::Tensor grad_out, torch::Tensor lr,
+                               bool mean, bool adagrad, double eps,
+                               std::optional<torch::Tensor> per_id_w,
+                               std::optional<torch::Tensor> sr,
+                               std::optional<torch::Tensor> adam_step,
+                               double beta1, double beta2,
+                               bool deterministic) {
+  const FusedApplyArgs args =
+      check_fused_apply(weight, state, grad_out, lr, adagrad, sr, adam_step,
+                        beta1, beta2, values.numel(), row_splits.numel() - 1);
+  // the plan's own checks of the ids come before its first launch
+  const SortPlan plan =
+      csr_sort_plan(values, row_splits, weight.size(0), mean, per_id_w);
+  apply_sort_plan(weight, state, plan, grad_out, lr, adagrad, eps, args,
+                  adam_step, beta1, beta2, deterministic);
 }
 
 // fp32 [n] -> bf16 [n], stochastically rounded with the bits the fused
@@ -1428,6 +1520,50 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("adagrad"), pybind11::arg("sr") = pybind11::none(),
         pybind11::arg("adam_step") = 0, pybind11::arg("beta1") = 0.9,
         pybind11::arg("beta2") = 0.999);
+  {
+    // an empty plan holds no tensors: its tensor attributes read as None
+    auto opt = [](const torch::Tensor& t) {
+      return t.defined() ? std::optional<torch::Tensor>(t) : std::nullopt;
+    };
+    pybind11::class_<SortPlan>(m, "SortPlan",
+                               "id-only half of the fused update, padded seg")
+        .def_readonly("nnz", &SortPlan::nnz)
+        .def_readonly("num_rows", &SortPlan::num_rows)
+        .def_readonly("vocab", &SortPlan::vocab)
+        .def_property_readonly(
+            "sorted_ids",
+            [opt](const SortPlan& p) { return opt(p.ss.sorted_ids); })
+        .def_property_readonly(
+            "srow", [opt](const SortPlan& p) { return opt(p.ss.srow); })
+        .def_property_readonly(
+            "sw", [opt](const SortPlan& p) { return opt(p.ss.sw); })
+        .def_property_readonly(
+            "seg", [opt](const SortPlan& p) { return opt(p.ss.seg); })
+        .def_property_readonly(
+            "unique_ids",
+            [opt](const SortPlan& p) { return opt(p.ss.unique_ids); })
+        .def_property_readonly(
+            "num_unique",
+            [opt](const SortPlan& p) { return opt(p.ss.num_unique); })
+        .def_property_readonly(
+            "bounds", [opt](const SortPlan& p) { return opt(p.ss.bounds); });
+  }
+  m.def("csr_sort_plan", &csr_sort_plan,
+        "id-only half of the fused update: sorted segments of a CSR batch, "
+        "seg padded (gfx950)",
+        pybind11::arg("values"), pybind11::arg("row_splits"),
+        pybind11::arg("vocab"), pybind11::arg("mean"),
+        pybind11::arg("per_id_w") = pybind11::none());
+  m.def("csr_fused_optimizer_apply_planned",
+        &csr_fused_optimizer_apply_planned,
+        "gradient half of the fused update on a csr_sort_plan (gfx950)",
+        pybind11::arg("weight"), pybind11::arg("state"), pybind11::arg("plan"),
+        pybind11::arg("grad_out"), pybind11::arg("lr"),
+        pybind11::arg("adagrad"), pybind11::arg("eps"),
+        pybind11::arg("sr") = pybind11::none(),
+        pybind11::arg("adam_step") = pybind11::none(),
+        pybind11::arg("beta1") = 0.9, pybind11::arg("beta2") = 0.999,
+        pybind11::arg("deterministic") = false);
   m.def("csr_fused_optimizer_apply", &csr_fused_optimizer_apply,
         "in-backward fused SGD/Adagrad/row-wise Adagrad/lazy Adam update "
         "(gfx950)",

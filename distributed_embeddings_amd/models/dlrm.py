@@ -31,6 +31,7 @@ from ..layers.embedding import Embedding, scaled_uniform_init
 from ..ops.cross import LowRankCrossNet, concat_packed
 from ..ops.dot_interact import dot_interact as fused_dot_interact
 from ..ops.dot_interact import dot_interact_packed
+from ..ops.embedding_lookup import hoisted_sort_plans
 from ..ops.mlp import MLP
 from ..parallel import comm
 from ..parallel.dist_embedding import DistributedEmbedding
@@ -221,15 +222,32 @@ class DLRM(nn.Module):
             # the (MFMA-bound) bottom MLP; autograd keeps the same streams
             # in backward, so the reverse all-to-all + table update overlap
             # the MLP grads too.  hipGraph capture spans the fork (world==1).
+            #
+            # DE_HOIST_SORT (default on): the id-only half of the fused
+            # update (the sort plan) is launched on the side stream right
+            # after the lookup instead of in the backward, where it sat on
+            # the step's tail (profiles/sort_hoist.md).  The main stream
+            # waits for the lookup alone; the backward of the lookup runs on
+            # the side stream, so after the plans, and the autograd engine
+            # joins that stream when backward() ends.
             if self._emb_stream is None:
                 self._emb_stream = torch.cuda.Stream()
             main = torch.cuda.current_stream()
             self._emb_stream.wait_stream(main)
+            hoist = os.environ.get("DE_HOIST_SORT", "1") != "0"
             with torch.cuda.stream(self._emb_stream):
-                packed, smaj = self.embeddings.forward_packed(
-                    cats, output_dtype=want, async_handle=handle)
+                with hoisted_sort_plans(hoist) as plans:
+                    packed, smaj = self.embeddings.forward_packed(
+                        cats, output_dtype=want, async_handle=handle)
+                if hoist:
+                    looked_up = torch.cuda.Event()
+                    looked_up.record()
+                    plans.build()
             bottom = self.bottom_mlp(numerical)
-            main.wait_stream(self._emb_stream)
+            if hoist:
+                main.wait_event(looked_up)
+            else:
+                main.wait_stream(self._emb_stream)
             if not torch.cuda.is_current_stream_capturing():
                 packed.record_stream(main)
             x = self._interact_packed(packed, bottom, smaj)

@@ -19,6 +19,7 @@ SparseAdam) apply O(nnz) updates.
 
 import contextlib
 import os
+import threading
 from typing import NamedTuple, Optional, Sequence, Tuple, Union
 
 import torch
@@ -604,6 +605,70 @@ def _lazy_adam_rows(state, ids, g, lr, beta1, beta2, eps, t):
     return m.mul_(-a_t).div_(v.sqrt_().add_(eps))
 
 
+# ---------------------------------------------------------------------------
+# Hoisted sort plans
+# ---------------------------------------------------------------------------
+#
+# The fused update starts with work that needs no gradient: the sort of the
+# ids and the segment of every unique id (``csr_sort_plan``).  Inside
+# ``hoisted_sort_plans()`` a fused lookup's forward registers a slot with the
+# plan's inputs; ``build()`` launches the plans on the current stream, and the
+# lookup's backward then only applies the update
+# (``csr_fused_optimizer_apply_planned``).  A caller with a side stream uses
+# it to build the plans beneath the forward's GEMMs.  Plans have to be built
+# and applied on one stream: the backward runs on the forward's stream, so
+# ``build()`` belongs on the stream the lookup ran on.
+
+_hoist = threading.local()
+
+
+class _PlanSlot:
+    """Inputs of one ``csr_sort_plan`` and, once built, the plan."""
+
+    __slots__ = ("inputs", "plan")
+
+    def __init__(self, values, row_splits, vocab, mean, w32):
+        self.inputs = (values, row_splits, vocab, mean, w32)
+        self.plan = None
+
+
+class SortPlanCollector:
+    """The slots the fused lookups registered inside one
+    :func:`hoisted_sort_plans` block."""
+
+    def __init__(self):
+        self.slots = []
+
+    def build(self) -> int:
+        """Launches ``csr_sort_plan`` for every registered slot on the
+        current stream and returns how many it launched.  Slots are built
+        once; a second call builds only what was registered since."""
+        slots, self.slots = self.slots, []
+        for slot in slots:
+            slot.plan = _backend.ops().csr_sort_plan(*slot.inputs)
+            slot.inputs = None
+        return len(slots)
+
+
+@contextlib.contextmanager
+def hoisted_sort_plans(enabled: bool = True):
+    """Context manager: fused GPU lookups whose backward will run register
+    their sort plan with the yielded :class:`SortPlanCollector` instead of
+    sorting in the backward.  The caller calls ``build()`` on the stream the
+    lookups ran on, any time before the backward; a slot that was never built
+    falls back to sorting in the backward.  With ``enabled`` false, with
+    gradients disabled and on the CPU nothing is registered and ``build()``
+    does nothing."""
+    collector = SortPlanCollector()
+    previous = getattr(_hoist, "collector", None)
+    _hoist.collector = collector if enabled and torch.is_grad_enabled() \
+        else None
+    try:
+        yield collector
+    finally:
+        _hoist.collector = previous
+
+
 class _CsrLookupFusedOptimizer(torch.autograd.Function):
     """CSR lookup whose backward applies the optimizer update in place.
 
@@ -660,7 +725,13 @@ class _CsrLookupFusedOptimizer(torch.autograd.Function):
         ctx.dw_dtype = per_id_w.dtype if need_dw else None
         # the backward runs in the mode the forward saw
         ctx.deterministic = is_deterministic()
+        ctx.plan_slot = None
         if weight.is_cuda:
+            collector = getattr(_hoist, "collector", None)
+            if collector is not None and any(ctx.needs_input_grad):
+                ctx.plan_slot = _PlanSlot(values, row_splits, weight.shape[0],
+                                          combiner == "mean", w32)
+                collector.slots.append(ctx.plan_slot)
             return _backend.ops().csr_lookup_forward(
                 weight, values, row_splits, combiner == "mean",
                 out_dtype == torch.bfloat16, w32,
@@ -682,7 +753,17 @@ class _CsrLookupFusedOptimizer(torch.autograd.Function):
             adam = ctx.adam
             # the kernels' condition for launching (and advancing the steps)
             launches = values.numel() > 0 and row_splits.numel() > 1
-            if weight.is_cuda and adam is not None:
+            slot = ctx.plan_slot
+            if slot is not None and slot.plan is not None:
+                # the sort ran in the forward (hoisted_sort_plans)
+                _backend.ops().csr_fused_optimizer_apply_planned(
+                    weight, state, slot.plan, grad_out, lr,
+                    ctx.adagrad, ctx.eps, sr,
+                    adam_step=None if adam is None else adam[0],
+                    beta1=0.9 if adam is None else adam[1],
+                    beta2=0.999 if adam is None else adam[2],
+                    deterministic=ctx.deterministic)
+            elif weight.is_cuda and adam is not None:
                 _backend.ops().csr_fused_optimizer_apply(
                     weight, state, values, row_splits, grad_out, lr,
                     ctx.combiner == "mean", False, ctx.eps, w32, sr,
