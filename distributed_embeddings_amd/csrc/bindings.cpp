@@ -703,26 +703,35 @@ static int64_t* sr_ptr(const std::optional<torch::Tensor>& sr,
   return t.data_ptr<int64_t>();
 }
 
-// Lazy Adam's moments: fp32 [2, vocab, width], m first, on the weight's
-// device; both betas in [0, 1).
-static void check_adam_state(const torch::Tensor& state,
+// Adam's moments, fp32 on the weight's device; both betas in [0, 1).  The
+// shape selects the rule: [2, vocab, width], m first, is lazy Adam, and a 1-D
+// state of vocab * (width + 1) elements, m [vocab, width] then the rows' v
+// [vocab], is partial row-wise Adam.  Returns true for the latter.
+static bool check_adam_state(const torch::Tensor& state,
                              const torch::Tensor& weight, double beta1,
                              double beta2) {
   CHECK_CUDA(state); CHECK_CONTIG(state);
   TORCH_CHECK(state.dtype() == torch::kFloat32, "adam state must be fp32");
-  TORCH_CHECK(state.dim() == 3 && state.size(0) == 2 &&
-              state.size(1) == weight.size(0) &&
-              state.size(2) == weight.size(1),
-              "adam state shape mismatch: expected [2, vocab, width], got ",
+  const bool lazy = state.dim() == 3 && state.size(0) == 2 &&
+                    state.size(1) == weight.size(0) &&
+                    state.size(2) == weight.size(1);
+  const bool rowwise =
+      state.dim() == 1 &&
+      state.size(0) == weight.size(0) * (weight.size(1) + 1);
+  TORCH_CHECK(lazy || rowwise,
+              "adam state shape mismatch: expected [2, vocab, width] (lazy "
+              "Adam) or [vocab * (width + 1)] (partial row-wise Adam), got ",
               state.sizes(), " for weight ", weight.sizes());
   TORCH_CHECK(state.device() == weight.device(),
               "adam state must be on the weight's device");
   TORCH_CHECK(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0,
               "adam betas must lie in [0, 1), got (", beta1, ", ", beta2, ")");
+  return rowwise;
 }
 
-// adam_step > 0 selects lazy Adam at step t = adam_step (the host counts on
-// this path): state is [2, vocab, width] and adagrad has to be false.
+// adam_step > 0 selects Adam at step t = adam_step (the host counts on this
+// path): adagrad has to be false, and state is [2, vocab, width] for lazy
+// Adam or [vocab * (width + 1)] for partial row-wise Adam.
 void sparse_row_update(torch::Tensor weight, torch::Tensor state,
                        torch::Tensor ids, torch::Tensor grad, double lr,
                        double eps, bool adagrad,
@@ -738,11 +747,10 @@ void sparse_row_update(torch::Tensor weight, torch::Tensor state,
   TORCH_CHECK(adam_step >= 0, "adam_step must not be negative");
   const bool adam = adam_step > 0;
   TORCH_CHECK(!(adam && adagrad), "adam_step and adagrad exclude each other");
-  if (adam) check_adam_state(state, weight, beta1, beta2);
+  bool rowwise = adam && check_adam_state(state, weight, beta1, beta2);
   const int64_t n = ids.numel();
   if (n == 0) return;
   float* state_ptr = nullptr;
-  bool rowwise = false;
   if (adagrad) {
     rowwise = check_adagrad_state(state, weight);
     state_ptr = state.data_ptr<float>();
@@ -800,7 +808,7 @@ SortPlan csr_sort_plan(torch::Tensor values, torch::Tensor row_splits,
 // What the apply has checked about its arguments.
 struct FusedApplyArgs {
   int64_t* sr_p;  // {seed, step} of stochastic rounding, or nullptr
-  bool rowwise;   // row-wise Adagrad state
+  bool rowwise;   // row-wise Adagrad or partial row-wise Adam state
 };
 
 // The one copy of the apply's argument checks; launches nothing.  nnz and
@@ -824,7 +832,7 @@ static FusedApplyArgs check_fused_apply(
   FusedApplyArgs args{sr_ptr(sr, weight), false};
   if (adam_step.has_value()) {
     TORCH_CHECK(!adagrad, "adam_step and adagrad exclude each other");
-    check_adam_state(state, weight, beta1, beta2);
+    args.rowwise = check_adam_state(state, weight, beta1, beta2);
     const torch::Tensor& t = *adam_step;
     CHECK_CUDA(t); CHECK_CONTIG(t);
     TORCH_CHECK(t.dtype() == torch::kInt64 && t.dim() == 1 && t.numel() == 1,
@@ -905,9 +913,10 @@ static void apply_sort_plan(torch::Tensor weight, torch::Tensor state,
 
 // The gradient half of the fused update on a csr_sort_plan.  Reads the plan's
 // tensors only and leaves them as they are, so one plan can be applied more
-// than once.  adam_step (int64 [1] on the device) selects lazy Adam: state is
-// [2, vocab, width], adagrad has to be false, and an apply that launches
-// adds 1 to the step on the device.
+// than once.  adam_step (int64 [1] on the device) selects Adam: state is
+// [2, vocab, width] (lazy Adam) or [vocab * (width + 1)] (partial row-wise
+// Adam), adagrad has to be false, and an apply that launches adds 1 to the
+// step on the device.
 void csr_fused_optimizer_apply_planned(torch::Tensor weight,
                                        torch::Tensor state,
                                        const SortPlan& plan,

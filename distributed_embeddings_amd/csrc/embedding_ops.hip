@@ -578,8 +578,9 @@ __device__ __forceinline__ float narrow_reduce(
 // Update rule of the element-wise kernels, a template parameter.
 enum : int { RULE_SGD = 0, RULE_ADAGRAD = 1, RULE_ADAM = 2 };
 
-// Lazy Adam's constants.  Its state is m [vocab, width] followed by v
-// [vocab, width]: the kernels get m's base and v_off = vocab * width.
+// Adam's constants.  The state is m [vocab, width] followed by v, which is
+// [vocab, width] for lazy Adam and [vocab], one per row, for partial row-wise
+// Adam: the kernels get m's base and v_off = vocab * width, where v starts.
 // omb = 1 - b, rounded once from double on the host.  The other rules carry
 // the struct unread.
 struct AdamArgs {
@@ -672,22 +673,81 @@ __device__ __forceinline__ float rowwise_denom(float* state, float ssq,
   return sqrtf(st) + eps;
 }
 
+// Partial row-wise Adam: lazy Adam with the second moment shared by the row,
+//   m[c] = b1 m[c] + (1 - b1) g[c];  v = b2 v + (1 - b2) mean_c(g[c]^2);
+//   w[c] -= a_t * m[c] / (sqrt(v) + eps),
+// a_t passed as lr like lazy Adam's.  The state is one array: m [vocab, width]
+// first, then v [vocab] at v_off = vocab * width.  The row-wise kernels take
+// the rule as a template parameter and the Adagrad instantiations are the
+// code they were.
+constexpr int RW_ADAGRAD = 0, RW_ADAM = 1;
+
+// rowwise_denom for the row's v: v = fma(b2, v, (1 - b2) * ssq / width), an
+// fma by name like adam_value's, and sqrt(v) + eps to every lane of the group.
+__device__ __forceinline__ float rowwise_adam_denom(float* v, float ssq,
+                                                    int width, int lane,
+                                                    int tile, bool live,
+                                                    float eps,
+                                                    const AdamArgs& ad) {
+  const int leader = lane & ~(tile - 1);
+  float st = 0.f;
+  if (live && lane == leader) {
+    st = __builtin_fmaf(ad.b2, *v, ad.omb2 * (ssq / (float)width));
+    *v = st;
+  }
+  st = __shfl(st, leader);
+  return sqrtf(st) + eps;
+}
+
+// The row's denominator under either rule; state is the kernel's state base.
+template <int RW>
+__device__ __forceinline__ float rowwise_rule_denom(float* state, int64_t uid,
+                                                    float ssq, int width,
+                                                    int lane, int tile,
+                                                    bool live, float eps,
+                                                    const AdamArgs& ad) {
+  if constexpr (RW == RW_ADAM)
+    return rowwise_adam_denom(&state[ad.v_off + uid], ssq, width, lane, tile,
+                              live, eps, ad);
+  else
+    return rowwise_denom(&state[uid], ssq, width, lane, tile, live, eps);
+}
+
+// The first moment and the weight step of one element: updates m, returns
+// the new w.
+__device__ __forceinline__ float rowwise_adam_value(float w, float& m, float g,
+                                                    float a_t, float denom,
+                                                    const AdamArgs& ad) {
+  m = __builtin_fmaf(ad.b1, m, ad.omb1 * g);
+  return w - a_t * m / denom;
+}
+
 // One wave applies one row whose summed gradient g[0..width) sits in memory
 // nobody writes during the kernel (the optimizer step's grad rows, the
 // finalize kernel's completed scratch rows): squares first, update second.
-// row0 is the table offset of w[0].
-template <typename PT>
+// row0 is the table offset of w[0], which is also where the row's m starts
+// in the Adam state.
+template <int RW, typename PT>
 __device__ __forceinline__ void rowwise_wave_update(
-    PT* __restrict__ w, float* __restrict__ state, const float* __restrict__ g,
-    int width, int lane, float lr, float eps, SrState sr, int64_t row0) {
+    PT* __restrict__ w, float* __restrict__ state, int64_t uid,
+    const float* __restrict__ g, int width, int lane, float lr, float eps,
+    SrState sr, int64_t row0, const AdamArgs& ad) {
   float ssq = 0.f;
   for (int c = lane; c < width; c += WAVE) ssq += g[c] * g[c];
   ssq = tile_sum(ssq, WAVE);
-  const float denom = rowwise_denom(state, ssq, width, lane, WAVE, true, eps);
+  const float denom =
+      rowwise_rule_denom<RW>(state, uid, ssq, width, lane, WAVE, true, eps, ad);
   for (int c = lane; c < width; c += WAVE) {
     const int64_t o = row0 + c;
-    pt_store_sr(&w[c], pt_load(&w[c]) - lr * g[c] / denom, sr,
-                sr_group_hash(sr, o), o);
+    float x;
+    if constexpr (RW == RW_ADAM) {
+      float m = state[o];
+      x = rowwise_adam_value(pt_load(&w[c]), m, g[c], lr, denom, ad);
+      state[o] = m;
+    } else {
+      x = pt_load(&w[c]) - lr * g[c] / denom;
+    }
+    pt_store_sr(&w[c], x, sr, sr_group_hash(sr, o), o);
   }
 }
 
@@ -1911,7 +1971,8 @@ __global__ void sorted_opt_update(PT* __restrict__ weight,
   }
 }
 
-// Row-wise Adagrad twin of sorted_opt_update.  A row's sum of squares has to
+// Row-wise twin of sorted_opt_update, for row-wise Adagrad and partial
+// row-wise Adam (RW).  A row's sum of squares has to
 // be complete before its first column moves, so the wide path walks the
 // columns twice: once for the squares, once for the update.  A row that fits
 // one column pass (width <= tile_w * VEC) keeps its sums in registers in
@@ -1919,7 +1980,8 @@ __global__ void sorted_opt_update(PT* __restrict__ weight,
 // column loops have wave-uniform trip counts, and a wide group with nothing
 // to do stays in step with live == false, because the lanes of one wave
 // shuffle together.
-template <int TILE, int VEC, bool HAS_W, bool SR, typename PT, typename GT>
+template <int TILE, int VEC, bool HAS_W, int RW, bool SR, typename PT,
+          typename GT>
 __global__ void sorted_opt_update_rowwise(
     PT* __restrict__ weight, float* __restrict__ state, float eps,
     const int64_t* __restrict__ sorted_ids, const int64_t* __restrict__ seg,
@@ -1927,7 +1989,7 @@ __global__ void sorted_opt_update_rowwise(
     const GT* __restrict__ grad_out, const float* __restrict__ lr_ptr,
     const int32_t* __restrict__ nu_ptr, int64_t long_thresh, int width,
     int64_t* __restrict__ long_rows, int32_t* __restrict__ long_count,
-    int tile_w, const int64_t* __restrict__ sr_ptr) {
+    int tile_w, const int64_t* __restrict__ sr_ptr, AdamArgs ad) {
   const WaveCoord wc = wave_coord();
   const TileCoord tc = tile_coord(wc.lane, TILE > 0 ? WAVE : tile_w);
   const float lr = *lr_ptr;
@@ -1955,12 +2017,19 @@ __global__ void sorted_opt_update_rowwise(
       // the fold leaves partial sums on lanes >= TILE: they count as 0
       const bool mine = wc.lane < TILE && wc.lane < width;
       const float ssq = tile_sum(mine ? g * g : 0.f, WAVE);
-      const float denom =
-          rowwise_denom(&state[uid], ssq, width, wc.lane, WAVE, true, eps);
+      const float denom = rowwise_rule_denom<RW>(state, uid, ssq, width,
+                                                 wc.lane, WAVE, true, eps, ad);
       if (mine) {
         const int64_t o = uid * (int64_t)width + wc.lane;
-        pt_store_sr(&wrow[wc.lane], pt_load(&wrow[wc.lane]) - lr * g / denom,
-                    sr, sr_group_hash(sr, o), o);
+        float x;
+        if constexpr (RW == RW_ADAM) {
+          float m = state[o];
+          x = rowwise_adam_value(pt_load(&wrow[wc.lane]), m, g, lr, denom, ad);
+          state[o] = m;
+        } else {
+          x = pt_load(&wrow[wc.lane]) - lr * g / denom;
+        }
+        pt_store_sr(&wrow[wc.lane], x, sr, sr_group_hash(sr, o), o);
       }
     } else {
       const int pass_w = tile_w * VEC;
@@ -1979,20 +2048,33 @@ __global__ void sorted_opt_update_rowwise(
         }
       }
       ssq = tile_sum(ssq, tile_w);
-      const float denom =
-          rowwise_denom(&state[uid], ssq, width, wc.lane, tile_w, live, eps);
+      const float denom = rowwise_rule_denom<RW>(
+          state, uid, ssq, width, wc.lane, tile_w, live, eps, ad);
       for (int p = 0; p < n_pass; ++p) {
         const int col0 = p * pass_w + tc.tl * VEC;
         if (live && col0 < width) {
           if (n_pass > 1)
             wide_accumulate<VEC, HAS_W, false>(grad_out, srow, sw, 0, width,
                                                col0, s, e, acc);
+          const int64_t o0 = uid * (int64_t)width + col0;
           float wv[VEC];
           pt_loadv<VEC>(wrow + col0, wv);
+          if constexpr (RW == RW_ADAM) {
+            // m goes whole into registers and whole back like w, one vector
+            // access each way (o0 is a multiple of VEC because width is):
+            // m and v share one array a runtime distance apart, see
+            // sorted_opt_update
+            float mv[VEC];
+            pt_loadv<VEC>(state + o0, mv);
 #pragma unroll
-          for (int v = 0; v < VEC; ++v) wv[v] -= lr * acc[v] / denom;
-          pt_storev_sr<VEC>(wrow + col0, wv, sr,
-                            uid * (int64_t)width + col0);
+            for (int v = 0; v < VEC; ++v)
+              wv[v] = rowwise_adam_value(wv[v], mv[v], acc[v], lr, denom, ad);
+            pt_storev<VEC>(state + o0, mv);
+          } else {
+#pragma unroll
+            for (int v = 0; v < VEC; ++v) wv[v] -= lr * acc[v] / denom;
+          }
+          pt_storev_sr<VEC>(wrow + col0, wv, sr, o0);
         }
       }
     }
@@ -2079,24 +2161,24 @@ __global__ void sorted_long_finalize(
   }
 }
 
-// Row-wise Adagrad finalize: the chunk kernel has completed the scratch row.
-template <bool SR, typename PT>
+// Row-wise finalize: the chunk kernel has completed the scratch row.
+template <int RW, bool SR, typename PT>
 __global__ void sorted_long_finalize_rowwise(
     PT* __restrict__ weight, float* __restrict__ state, float eps,
     const int64_t* __restrict__ sorted_ids, const int64_t* __restrict__ seg,
     const float* __restrict__ lr_ptr, int width,
     const int64_t* __restrict__ long_rows,
     const int32_t* __restrict__ long_count, const float* __restrict__ scratch,
-    const int64_t* __restrict__ sr_ptr) {
+    const int64_t* __restrict__ sr_ptr, AdamArgs ad) {
   const WaveCoord wc = wave_coord();
   const float lr = *lr_ptr;
   const int64_t n_long = *long_count;
   const SrState sr = sr_load<SR>(sr_ptr);
   for (int64_t li = wc.wave_id; li < n_long; li += wc.n_waves) {
     const int64_t uid = sorted_ids[seg[long_rows[li]]];
-    rowwise_wave_update(weight + uid * (int64_t)width, &state[uid],
-                        scratch + li * (int64_t)width, width, wc.lane, lr, eps,
-                        sr, uid * (int64_t)width);
+    rowwise_wave_update<RW>(weight + uid * (int64_t)width, state, uid,
+                            scratch + li * (int64_t)width, width, wc.lane, lr,
+                            eps, sr, uid * (int64_t)width, ad);
   }
 }
 
@@ -2150,11 +2232,14 @@ static void launch_sorted_optimizer_update_t(
     dispatch_bool(sw != nullptr, [&](auto has_w_t) {
       constexpr bool HAS_W = decltype(has_w_t)::value;
       if (rowwise) {
-        hipLaunchKernelGGL(
-            (sorted_opt_update_rowwise<TILE, VEC, HAS_W, SR, PT, GT>), grid,
-            block, 0, stream, weight, state, eps, sorted_ids, seg, srow, sw,
-            grad_out, lr, nu_ptr, (int64_t)LONG_T, width, long_rows,
-            long_count, t.tile_w, sr);
+        dispatch_bool(rule == RULE_ADAM, [&](auto adam_t) {
+          constexpr int RW = decltype(adam_t)::value ? RW_ADAM : RW_ADAGRAD;
+          hipLaunchKernelGGL(
+              (sorted_opt_update_rowwise<TILE, VEC, HAS_W, RW, SR, PT, GT>),
+              grid, block, 0, stream, weight, state, eps, sorted_ids, seg,
+              srow, sw, grad_out, lr, nu_ptr, (int64_t)LONG_T, width,
+              long_rows, long_count, t.tile_w, sr, ad);
+        });
       } else {
         dispatch_rule(rule, [&](auto rule_t) {
           hipLaunchKernelGGL(
@@ -2190,9 +2275,13 @@ static void launch_sorted_optimizer_update_t(
       });
     });
     if (rowwise)
-      hipLaunchKernelGGL((sorted_long_finalize_rowwise<SR, PT>), dim3(256),
-                         block, 0, stream, weight, state, eps, sorted_ids, seg,
-                         lr, width, long_rows, long_count, long_scratch, sr);
+      dispatch_bool(rule == RULE_ADAM, [&](auto adam_t) {
+        constexpr int RW = decltype(adam_t)::value ? RW_ADAM : RW_ADAGRAD;
+        hipLaunchKernelGGL((sorted_long_finalize_rowwise<RW, SR, PT>),
+                           dim3(256), block, 0, stream, weight, state, eps,
+                           sorted_ids, seg, lr, width, long_rows, long_count,
+                           long_scratch, sr, ad);
+      });
     else if (use_scratch)
       dispatch_rule(rule, [&](auto rule_t) {
         hipLaunchKernelGGL(
@@ -2241,8 +2330,8 @@ void launch_sorted_optimizer_update(void* weight, bool weight_bf16,
         launch_sorted_optimizer_update_t<decltype(sr_t)::value>(
             (PT*)weight, state, eps, sorted_ids, seg, srow, sw,
             (const GT*)grad_out, lr, nu_ptr, max_segs, width, long_rows,
-            long_count, work_items, n_work, long_scratch, rule,
-            rowwise && !adam, sr, adam_args(adam, width), det, stream);
+            long_count, work_items, n_work, long_scratch, rule, rowwise, sr,
+            adam_args(adam, width), det, stream);
       });
     });
   });
@@ -2369,22 +2458,21 @@ __global__ void sparse_row_update(PT* __restrict__ weight,
   }
 }
 
-// Row-wise Adagrad: state is [vocab], one float per row.
-template <bool SR, typename PT>
-__global__ void sparse_row_update_rowwise(PT* __restrict__ weight,
-                                          float* __restrict__ state,
-                                          const int64_t* __restrict__ ids,
-                                          const float* __restrict__ grad,
-                                          int64_t num_rows, int width,
-                                          float lr, float eps,
-                                          const int64_t* __restrict__ sr_ptr) {
+// Row-wise Adagrad: state is [vocab], one float per row.  Partial row-wise
+// Adam: state is m [vocab, width] then v [vocab], and lr is a_t.
+template <int RW, bool SR, typename PT>
+__global__ void sparse_row_update_rowwise(
+    PT* __restrict__ weight, float* __restrict__ state,
+    const int64_t* __restrict__ ids, const float* __restrict__ grad,
+    int64_t num_rows, int width, float lr, float eps,
+    const int64_t* __restrict__ sr_ptr, AdamArgs ad) {
   const WaveCoord wc = wave_coord();
   const SrState sr = sr_load<SR>(sr_ptr);
   for (int64_t r = wc.wave_id; r < num_rows; r += wc.n_waves) {
     const int64_t uid = ids[r];
-    rowwise_wave_update(weight + uid * (int64_t)width, &state[uid],
-                        grad + r * (int64_t)width, width, wc.lane, lr, eps, sr,
-                        uid * (int64_t)width);
+    rowwise_wave_update<RW>(weight + uid * (int64_t)width, state, uid,
+                            grad + r * (int64_t)width, width, wc.lane, lr, eps,
+                            sr, uid * (int64_t)width, ad);
   }
 }
 
@@ -2398,15 +2486,18 @@ void launch_sparse_row_update(void* weight, bool weight_bf16, float* state,
   if (!weight_bf16) sr = nullptr;  // fp32 tables do not round
   const int rule = adam ? RULE_ADAM : adagrad ? RULE_ADAGRAD : RULE_SGD;
   const AdamArgs ad = adam_args(adam, width);
-  if (adam) rowwise = false;
   dispatch_bool(weight_bf16, [&](auto w_bf16) {
     using PT = storage_t<decltype(w_bf16)>;
     dispatch_sr<PT>(sr, [&](auto sr_t) {
       constexpr bool SR = decltype(sr_t)::value;
       if (rowwise) {
-        hipLaunchKernelGGL((sparse_row_update_rowwise<SR, PT>), dim3(grid),
-                           dim3(block), 0, stream, (PT*)weight, state, ids,
-                           grad, num_rows, width, lr, eps, sr);
+        dispatch_bool(adam != nullptr, [&](auto adam_t) {
+          constexpr int RW = decltype(adam_t)::value ? RW_ADAM : RW_ADAGRAD;
+          hipLaunchKernelGGL((sparse_row_update_rowwise<RW, SR, PT>),
+                             dim3(grid), dim3(block), 0, stream, (PT*)weight,
+                             state, ids, grad, num_rows, width, lr, eps, sr,
+                             ad);
+        });
         return;
       }
       dispatch_rule(rule, [&](auto rule_t) {

@@ -120,12 +120,15 @@ void launch_hash_reinsert(const int64_t* old_keys, const int64_t* old_vals,
 void launch_pad_seg_offsets(int64_t* seg, int64_t n, const int32_t* num_unique,
                             const int64_t* valid_end, hipStream_t stream);
 
-// Lazy Adam.  state is then fp32 [2, vocab, width], m first, and adagrad and
-// rowwise are ignored.  launch_sorted_optimizer_update: a leading one-thread
+// Lazy Adam.  state is then fp32 [2, vocab, width], m first, adagrad is
+// ignored and rowwise is false.  launch_sorted_optimizer_update: a leading one-thread
 // kernel sets t = ++step[0] and a_t[0] = lr * sqrt(1 - b2^t) / (1 - b1^t) on
 // the device (step: int64 [1], a_t: one float of scratch) and the update
 // kernels read a_t in place of lr.  launch_sparse_row_update leaves step and
 // a_t alone: its caller passes a_t as lr.
+// Partial row-wise Adam: adam together with rowwise.  state is then fp32
+// [vocab * width + vocab], m [vocab, width] first and the rows' second
+// moments v [vocab] behind it; step and a_t as for lazy Adam.
 struct AdamConfig {
   double b1, b2;
   int64_t vocab;
@@ -135,7 +138,7 @@ struct AdamConfig {
 
 // adam == nullptr selects SGD or Adagrad by the flags.
 // rowwise (row-wise Adagrad) takes state as [vocab] fp32, one float per row,
-// in place of Adagrad's [vocab, width]; it implies adagrad.
+// in place of Adagrad's [vocab, width]; without adam it implies adagrad.
 // sr: device pointer to {seed, step}, or nullptr.  With a bf16 weight it
 // selects stochastic rounding of the weight stores; every kernel of the call
 // reads the same step and a trailing one-thread kernel adds 1 to it, which is

@@ -21,9 +21,13 @@ from ..ops.embedding_lookup import (Ragged, _csr_lookup_q8,
                                     _check_bits, _check_packed,
                                     dequantize_rowwise_int4,
                                     dequantize_rowwise_int8, embedding_lookup,
+                                    partial_rowwise_adam_views,
                                     quantize_rowwise_int4,
                                     quantize_rowwise_int8,
                                     quantized_embedding_lookup, to_int64)
+
+# fused methods with a step counter and betas
+_ADAM_METHODS = ("lazy_adam", "partial_rowwise_adam")
 
 
 def _default_init(weight: torch.Tensor) -> None:
@@ -222,8 +226,8 @@ class Embedding(nn.Module):
         ``method`` is ``"sgd"``, ``"adagrad"`` (fp32 state
         ``[input_dim, output_dim]``), ``"rowwise_adagrad"`` (fp32 state
         ``[input_dim]``: one accumulator per row, fed with the mean square of
-        the row's summed gradient) or ``"lazy_adam"``.  Calling it again
-        replaces the state.
+        the row's summed gradient), ``"lazy_adam"`` or
+        ``"partial_rowwise_adam"``.  Calling it again replaces the state.
 
         ``"lazy_adam"`` is ``torch.optim.SparseAdam``'s update with ``betas``
         (each in ``[0, 1)``, else ``ValueError``): rows whose id occurs in
@@ -238,6 +242,14 @@ class Embedding(nn.Module):
         continues at the right ``t``.  ``eps`` keeps its Adagrad default of
         ``1e-10``; Adam users normally pass ``1e-8``.
 
+        ``"partial_rowwise_adam"`` is lazy Adam with one second moment per
+        row (FBGEMM's ``PARTIAL_ROWWISE_ADAM``): ``v[u] = b2 v[u] + (1 - b2)
+        mean_c(G[u, c]^2)``, with ``m``, ``t``, ``betas`` and the weight step
+        as above.  Its state is one flat fp32 buffer ``_fused_state``
+        ``[input_dim * (output_dim + 1)]``, 4 + 4 / output_dim bytes per
+        table element: ``m`` ``[input_dim, output_dim]`` first, then ``v``
+        ``[input_dim]``.  ``fused_moments()`` returns the two as views.
+
         ``stochastic_rounding`` (bf16 tables only; ``ValueError`` on fp32)
         stores the updated weights with stochastic instead of nearest-even
         rounding, so updates below half a bf16 ulp of the weight survive on
@@ -247,7 +259,8 @@ class Embedding(nn.Module):
         ``state_dict``, so a resumed run continues the bit stream.
         ``seed=None`` draws the seed from torch's default CPU generator
         (``torch.manual_seed`` makes runs repeatable)."""
-        if method not in ("sgd", "adagrad", "rowwise_adagrad", "lazy_adam"):
+        if method not in ("sgd", "adagrad", "rowwise_adagrad", "lazy_adam",
+                          "partial_rowwise_adam"):
             raise ValueError(f"unknown fused optimizer {method!r}")
         check_betas(betas)
         if self.quantized:
@@ -266,10 +279,12 @@ class Embedding(nn.Module):
         self._fused_method = method
         self._fused_eps = float(eps)
         self._fused_betas = (float(betas[0]), float(betas[1]))
-        if method == "lazy_adam":
+        if method in _ADAM_METHODS:
+            vocab, width = self.weight.shape
+            shape = ((2, vocab, width) if method == "lazy_adam"
+                     else (vocab * (width + 1),))
             self.register_buffer("_fused_state",
-                                 torch.zeros((2,) + tuple(self.weight.shape),
-                                             dtype=torch.float32,
+                                 torch.zeros(shape, dtype=torch.float32,
                                              device=self.weight.device))
             self.register_buffer("_fused_step",
                                  torch.zeros(1, dtype=torch.int64,
@@ -289,7 +304,7 @@ class Embedding(nn.Module):
         # weight itself carries de_local when model-parallel)
         self._fused_state.de_local = getattr(self.weight, "de_local", False)
         self._fused_lr.de_local = False  # lr is global; broadcasting is fine
-        if method == "lazy_adam":
+        if method in _ADAM_METHODS:
             self._fused_step.de_local = self._fused_state.de_local
         if stochastic_rounding:
             if seed is None:
@@ -301,6 +316,20 @@ class Embedding(nn.Module):
             # the bit stream belongs to the shard, like the optimizer state
             self._fused_sr.de_local = self._fused_state.de_local
         return self
+
+    def fused_moments(self):
+        """``(m, v)`` of the fused Adam state as views of ``_fused_state``:
+        both ``[input_dim, output_dim]`` for ``"lazy_adam"``; ``m``
+        ``[input_dim, output_dim]`` and ``v`` ``[input_dim]`` for
+        ``"partial_rowwise_adam"``."""
+        method = getattr(self, "_fused_method", None)
+        if method not in _ADAM_METHODS:
+            raise RuntimeError("fused_moments() needs a fused Adam method, "
+                               f"got {method!r}")
+        if method == "lazy_adam":
+            return self._fused_state[0], self._fused_state[1]
+        return partial_rowwise_adam_views(self._fused_state,
+                                          *self.weight.shape)
 
     def set_fused_lr(self, lr: float):
         if self.quantized:
@@ -330,7 +359,7 @@ class Embedding(nn.Module):
                                       self.quantized_bits)
         if getattr(self, "_fused_lr", None) is not None and self.training:
             adam = None
-            if self._fused_method == "lazy_adam":
+            if self._fused_method in _ADAM_METHODS:
                 adam = (self._fused_step,) + self._fused_betas
             return csr_lookup_fused_optimizer(
                 self.weight, values, row_splits, combiner, self._fused_lr,

@@ -581,10 +581,13 @@ def _check_adam(adam, adagrad, state, weight) -> None:
         raise ValueError("adam and adagrad exclude each other")
     check_betas((beta1, beta2))
     if (state.dtype != torch.float32 or state.device != weight.device
-            or state.shape != (2,) + tuple(weight.shape)):
-        raise ValueError("lazy Adam needs an fp32 state [2, vocab, width] on "
-                         f"the weight's device, got {tuple(state.shape)} "
-                         f"{state.dtype} for weight {tuple(weight.shape)}")
+            or (state.shape != (2,) + tuple(weight.shape)
+                and not _is_partial_rowwise(state, weight))):
+        raise ValueError("Adam needs an fp32 state on the weight's device, "
+                         "[2, vocab, width] (lazy Adam) or "
+                         "[vocab * (width + 1)] (partial row-wise Adam), got "
+                         f"{tuple(state.shape)} {state.dtype} for weight "
+                         f"{tuple(weight.shape)}")
     if (step.dtype != torch.int64 or step.shape != (1,)
             or step.device != weight.device):
         raise ValueError("the Adam step must be an int64 [1] tensor on the "
@@ -603,6 +606,39 @@ def _lazy_adam_rows(state, ids, g, lr, beta1, beta2, eps, t):
     state[1].index_copy_(0, ids, v)
     a_t = lr * (1.0 - beta2 ** t) ** 0.5 / (1.0 - beta1 ** t)
     return m.mul_(-a_t).div_(v.sqrt_().add_(eps))
+
+
+def _is_partial_rowwise(state, weight) -> bool:
+    """True for partial row-wise Adam's state: 1-D, ``vocab * (width + 1)``."""
+    return (state.dim() == 1 and weight.dim() == 2
+            and state.numel() == weight.shape[0] * (weight.shape[1] + 1))
+
+
+def partial_rowwise_adam_views(state, vocab, width):
+    """``(m, v)`` of partial row-wise Adam's flat state as views: the first
+    moments ``[vocab, width]`` and, behind them, the rows' second moments
+    ``[vocab]``."""
+    n = vocab * width
+    return state[:n].view(vocab, width), state[n:]
+
+
+def _partial_rowwise_adam_rows(state, ids, g, lr, beta1, beta2, eps, t):
+    """Partial row-wise Adam at step ``t`` on the rows ``ids`` (unique) of the
+    flat fp32 state (:func:`partial_rowwise_adam_views`) with their fp32
+    summed gradients ``g`` ``[len(ids), width]``: lazy Adam with one second
+    moment per row, fed with the mean square of the row's gradient.  Updates
+    ``m`` and ``v`` of those rows in place and returns the rows' weight
+    delta.  The fp32 torch-op form of the update the HIP kernels apply."""
+    width = g.shape[1]
+    m_all, v_all = partial_rowwise_adam_views(
+        state, state.numel() // (width + 1), width)
+    m = m_all.index_select(0, ids).mul_(beta1).add_(g, alpha=1.0 - beta1)
+    v = v_all.index_select(0, ids).mul_(beta2).add_(
+        (g * g).mean(dim=1), alpha=1.0 - beta2)
+    m_all.index_copy_(0, ids, m)
+    v_all.index_copy_(0, ids, v)
+    a_t = lr * (1.0 - beta2 ** t) ** 0.5 / (1.0 - beta1 ** t)
+    return m.mul_(-a_t).div_(v.sqrt_().add_(eps).unsqueeze(1))
 
 
 # ---------------------------------------------------------------------------
@@ -705,6 +741,13 @@ class _CsrLookupFusedOptimizer(torch.autograd.Function):
 
     in fp32, which is ``torch.optim.SparseAdam``'s update.  Rows whose id
     does not occur keep ``w``, ``m`` and ``v`` bit for bit.
+
+    With ``adam`` set, a 1-D fp32 state of ``vocab * (width + 1)`` elements
+    selects partial row-wise Adam: ``m`` ``[vocab, width]`` first, then one
+    second moment per row, ``v`` ``[vocab]``
+    (:func:`partial_rowwise_adam_views`).  The update is the one above with
+    ``v[u] = b2 v[u] + (1 - b2) mean_c(G[u, c]^2)`` shared by the row's
+    columns.
     """
 
     @staticmethod
@@ -784,7 +827,10 @@ class _CsrLookupFusedOptimizer(torch.autograd.Function):
                     if launches:
                         step = adam[0]
                         step += 1
-                        delta = _lazy_adam_rows(
+                        rows_fn = (_partial_rowwise_adam_rows
+                                   if _is_partial_rowwise(state, weight)
+                                   else _lazy_adam_rows)
+                        delta = rows_fn(
                             state, unique_ids, unique_grad, lr_v, adam[1],
                             adam[2], ctx.eps, int(step))
                 elif ctx.adagrad:

@@ -269,7 +269,8 @@ class DistributedEmbedding(nn.Module):
                                seed: Optional[int] = None,
                                betas=(0.9, 0.999)):
         """Enables the in-backward fused optimizer (``"sgd"``, ``"adagrad"``,
-        ``"rowwise_adagrad"`` or ``"lazy_adam"``, which takes ``betas``) on
+        ``"rowwise_adagrad"``, or ``"lazy_adam"`` or
+        ``"partial_rowwise_adam"``, which take ``betas``) on
         all model-parallel tables (col + row groups).  Data-parallel tables keep sparse grads (they need the
         allreduce); CPU-offloaded tables keep sparse grads too (their lookup
         runs through the CPU fallback, not the HIP fused kernel).
@@ -286,6 +287,11 @@ class DistributedEmbedding(nn.Module):
         depend on that element's summed gradient alone, and every shard
         counts the same steps.  Row-sliced and column-sliced shards
         therefore train exactly like the undistributed table.
+
+        Partial row-wise Adam keeps ``m`` per element and ``v`` per row, and
+        its state follows the shard like row-wise Adagrad's: a row-sliced
+        shard trains like the undistributed table, a column-sliced shard
+        takes the row mean of the squares over its own columns.
 
         ``stochastic_rounding`` (bf16 tables, ``table_dtype=torch.bfloat16``)
         and ``seed`` are the layer's.  Every local layer gets a seed of its

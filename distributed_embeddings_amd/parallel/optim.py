@@ -16,19 +16,20 @@ the reference examples' per-variable optimizer usage (SGD in
 import torch
 
 from ..ops import _backend
-from ..ops.embedding_lookup import (_lazy_adam_rows, _write_rows_sr,
+from ..ops.embedding_lookup import (_lazy_adam_rows,
+                                    _partial_rowwise_adam_rows, _write_rows_sr,
                                     check_betas, mix64_int, to_int64)
 
 
 class SparseEmbeddingOptimizer(torch.optim.Optimizer):
-    """SGD / Adagrad / row-wise Adagrad / lazy Adam with fused sparse row
-    updates.
+    """SGD / Adagrad / row-wise Adagrad / lazy Adam / partial row-wise Adam
+    with fused sparse row updates.
 
     Args:
       params: iterable of parameters (dense and sparse-grad mixed).
       lr: learning rate.
-      method: ``"sgd"``, ``"adagrad"``, ``"rowwise_adagrad"`` or
-        ``"lazy_adam"``.  Row-wise
+      method: ``"sgd"``, ``"adagrad"``, ``"rowwise_adagrad"``,
+        ``"lazy_adam"`` or ``"partial_rowwise_adam"``.  Row-wise
         Adagrad keeps one fp32 accumulator per row of a sparse-grad param
         (state ``[vocab]``), fed with the mean square of the row's gradient.
         Dense-grad params in the same optimizer keep element-wise Adagrad.
@@ -42,6 +43,12 @@ class SparseEmbeddingOptimizer(torch.optim.Optimizer):
         elements; their ``state[p]["step"]`` is a 0-dim float64 tensor on
         the param's device, so a hipGraph-captured ``step()`` takes a new
         ``t`` on every replay.
+        Partial row-wise Adam is lazy Adam with one second moment per row of
+        a sparse-grad param, ``v[u] = b2 v[u] + (1 - b2) mean_c(g[u, c]^2)``:
+        ``state[p]["exp_avgs"]`` is then flat, ``[vocab * (width + 1)]``,
+        ``exp_avg`` ``[vocab, width]`` first and the rows' ``v`` ``[vocab]``
+        behind it.  Dense-grad params in the same optimizer keep
+        element-wise Adam.
       eps: adagrad / adam epsilon (Adam users normally pass ``1e-8``).
       betas: lazy Adam's ``(b1, b2)``, each in ``[0, 1)``.
       assume_coalesced: trust that every sparse grad holds unique, sorted ids
@@ -65,7 +72,8 @@ class SparseEmbeddingOptimizer(torch.optim.Optimizer):
                  eps: float = 1e-10, assume_coalesced: bool = True,
                  stochastic_rounding: bool = False, seed=None,
                  betas=(0.9, 0.999)):
-        if method not in ("sgd", "adagrad", "rowwise_adagrad", "lazy_adam"):
+        if method not in ("sgd", "adagrad", "rowwise_adagrad", "lazy_adam",
+                          "partial_rowwise_adam"):
             raise ValueError(f"unknown method {method!r}")
         check_betas(betas)
         if stochastic_rounding and seed is None:
@@ -111,7 +119,8 @@ class SparseEmbeddingOptimizer(torch.optim.Optimizer):
             eps = group["eps"]
             adagrad = group["method"] in ("adagrad", "rowwise_adagrad")
             rowwise = group["method"] == "rowwise_adagrad"
-            adam = group["method"] == "lazy_adam"
+            adam = group["method"] in ("lazy_adam", "partial_rowwise_adam")
+            adam_rowwise = group["method"] == "partial_rowwise_adam"
             betas = group.get("betas", (0.9, 0.999))
             dense = []
             for p in group["params"]:
@@ -125,7 +134,8 @@ class SparseEmbeddingOptimizer(torch.optim.Optimizer):
                         sr = self._sr_for(p, group["seed"])
                     if adam:
                         self._sparse_adam(p, g, lr, eps, betas,
-                                          group["assume_coalesced"], sr)
+                                          group["assume_coalesced"], sr,
+                                          adam_rowwise)
                         continue
                     self._sparse_update(p, g, lr, eps, adagrad, rowwise,
                                         group["assume_coalesced"], sr)
@@ -145,12 +155,15 @@ class SparseEmbeddingOptimizer(torch.optim.Optimizer):
                                     dtype=torch.float32, device=p.device)
         return st["sum"]
 
-    def _adam_state_for(self, p, device_step=False):
-        """(moments [2, *p.shape] fp32, the step counter before this
-        update): a host int, or with device_step a 0-dim float64 tensor."""
+    def _adam_state_for(self, p, device_step=False, rowwise=False):
+        """(moments fp32, the step counter before this update): [2, *p.shape],
+        or with rowwise the flat [vocab * (width + 1)] of partial row-wise
+        Adam; a host int, or with device_step a 0-dim float64 tensor."""
         st = self.state[p]
         if "exp_avgs" not in st:
-            st["exp_avgs"] = torch.zeros((2,) + tuple(p.shape),
+            shape = ((p.shape[0] * (p.shape[1] + 1),) if rowwise
+                     else (2,) + tuple(p.shape))
+            st["exp_avgs"] = torch.zeros(shape,
                                          dtype=torch.float32, device=p.device)
             st["step"] = (torch.zeros((), dtype=torch.float64, device=p.device)
                           if device_step else 0)
@@ -197,22 +210,25 @@ class SparseEmbeddingOptimizer(torch.optim.Optimizer):
                 rows = p.data.index_select(0, ids).float() + delta
                 _write_rows_sr(p.data, ids, rows, sr)
 
-    def _sparse_adam(self, p, g, lr, eps, betas, assume_coalesced, sr=None):
+    def _sparse_adam(self, p, g, lr, eps, betas, assume_coalesced, sr=None,
+                     rowwise=False):
         if not (assume_coalesced or g.is_coalesced()):
             g = g.coalesce()
         ids = g._indices()[0]
         vals = g._values().float()
         if ids.numel() == 0:
             return  # nothing applied: t stays, like the fused path's
-        state, t = self._adam_state_for(p)
+        rowwise = rowwise and p.dim() == 2
+        state, t = self._adam_state_for(p, rowwise=rowwise)
         t = self.state[p]["step"] = int(t) + 1
         if p.is_cuda:
+            # the kernel reads the rule off the state's shape
             _backend.ops().sparse_row_update(
                 p.data, state, ids.contiguous(), vals.contiguous(), lr, eps,
                 False, sr, adam_step=t, beta1=betas[0], beta2=betas[1])
             return
-        delta = _lazy_adam_rows(state, ids, vals, lr, betas[0], betas[1], eps,
-                                t)
+        rows_fn = _partial_rowwise_adam_rows if rowwise else _lazy_adam_rows
+        delta = rows_fn(state, ids, vals, lr, betas[0], betas[1], eps, t)
         if sr is None:
             p.data.index_add_(0, ids, delta.to(p.dtype))
         else:

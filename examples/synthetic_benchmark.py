@@ -38,10 +38,12 @@ def parse_args():
     p.add_argument("--column-slice-threshold", type=int, default=None)
     p.add_argument("--dp-input", action="store_true", default=True)
     p.add_argument("--optimizer", default="adagrad",
-                   choices=["adagrad", "rowwise_adagrad", "sgd", "lazy_adam"],
+                   choices=["adagrad", "rowwise_adagrad", "sgd", "lazy_adam",
+                            "partial_rowwise_adam"],
                    help="lazy_adam is the reference benchmark's adam: "
                         "SparseAdam's update, 8 B of fp32 moments per table "
-                        "element")
+                        "element; partial_rowwise_adam keeps the second "
+                        "moment per row, 4 + 4/width B per element")
     p.add_argument("--pool", type=int, default=4)
     p.add_argument("--graph", dest="graph", action="store_true", default=True,
                    help="hipGraph-capture the step (world==1; eager fallback)")
@@ -103,7 +105,7 @@ def main():
                 zip(torch.split(flat, cat_sizes), cat_shapes)]
 
     # Adam's customary eps; the Adagrad methods keep the optimizers' default
-    eps = 1e-8 if args.optimizer == "lazy_adam" else 1e-10
+    eps = 1e-8 if args.optimizer.endswith("adam") else 1e-10
     opt = de.DistributedOptimizer(SparseEmbeddingOptimizer(
         model.parameters(), lr=0.01, method=args.optimizer, eps=eps),
         average=False)

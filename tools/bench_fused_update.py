@@ -19,7 +19,8 @@ same inputs.  --stochastic-rounding (bf16 tables) times every method twice,
 with nearest-even and with stochastic rounding, the two alternating inside
 every round like the methods.  lazy_adam needs this tree's build: its state
 is the [2, VOCAB, WIDTH] moments (10 GB) and it counts its steps in a device
-tensor.
+tensor.  partial_rowwise_adam likewise, with the flat [VOCAB * (WIDTH + 1)]
+state (5 GB).
 
 --deterministic times this tree's build in deterministic mode (long segments
 through the slab and the fixed-order combine, no float atomics); the line then
@@ -39,7 +40,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 
 VOCAB, WIDTH, NNZ = 10_000_000, 128, 1_700_000
-METHODS = ("sgd", "adagrad", "rowwise_adagrad", "lazy_adam")
+METHODS = ("sgd", "adagrad", "rowwise_adagrad", "lazy_adam",
+           "partial_rowwise_adam")
 ID_SETS = ("uniform", "power_law", "tiny_vocab", "all_equal")
 
 
@@ -58,6 +60,8 @@ def state_for(method):
         return torch.empty(0, device="cuda")
     if method == "lazy_adam":
         return torch.zeros(2, VOCAB, WIDTH, device="cuda")
+    if method == "partial_rowwise_adam":
+        return torch.zeros(VOCAB * (WIDTH + 1), device="cuda")
     shape = (VOCAB, WIDTH) if method == "adagrad" else (VOCAB,)
     return torch.zeros(shape, device="cuda")
 
@@ -113,7 +117,7 @@ def main():
         splits, grad = all_splits[:n + 1], all_grad[:n]
         # the nearest-even call is the parent commit's, argument for argument
         extra = (None, sr) if rounding == "sr" else ()
-        if method == "lazy_adam":
+        if method in ("lazy_adam", "partial_rowwise_adam"):
             ext.csr_fused_optimizer_apply(w, states[method], ids, splits, grad,
                                           lr, False, False, 1e-8, *extra,
                                           adam_step=adam_step, **det)
