@@ -1454,6 +1454,41 @@ std::vector<int64_t> wgrad_splitk_plan_py(int64_t K, int64_t M, int64_t N) {
   return {plan.use ? 1 : 0, plan.splitk, plan.cfg};
 }
 
+// Weight and bias gradient of a Linear with one output feature
+// (wgrad_splitk.hip): (gw [1, N], gb [1]) = (bf16(g^T x), bf16(sum g)) for
+// g [K, 1], x [K, N].  Slab from the torch allocator, both launches on the
+// current stream: capturable.
+std::vector<torch::Tensor> wgrad_gemv(torch::Tensor g, torch::Tensor x) {
+  CHECK_CUDA(g); CHECK_CUDA(x);
+  CHECK_CONTIG(g); CHECK_CONTIG(x);
+  TORCH_CHECK(g.dtype() == torch::kBFloat16 && x.dtype() == torch::kBFloat16,
+              "bf16 required");
+  TORCH_CHECK(g.dim() == 2 && x.dim() == 2 && g.size(1) == 1 &&
+              g.size(0) == x.size(0), "g must be [K, 1] and x [K, N]");
+  TORCH_CHECK(g.device() == x.device(), "operands must share a device");
+  const int64_t K = g.size(0), N = x.size(1);
+  WgradGemvPlan plan;
+  TORCH_CHECK(wgrad_gemv_plan(K, N, &plan),
+              "wgrad_gemv takes K >= 1 and N % 8 == 0; got K=", K, " N=", N);
+  CHECK_ALIGN16(x);
+  auto gw = torch::empty({1, N}, g.options());
+  auto gb = torch::empty({1}, g.options());
+  auto slab = torch::empty({plan.num_chunks, N + 1},
+                           g.options().dtype(torch::kFloat32));
+  launch_wgrad_gemv(g.data_ptr(), x.data_ptr(), slab.data_ptr<float>(),
+                    gw.data_ptr(), gb.data_ptr(), K, (int)N, plan,
+                    current_stream());
+  return {gw, gb};
+}
+
+// (use, row chunks) of the plan; use == false also for shapes the kernels do
+// not take
+std::vector<int64_t> wgrad_gemv_plan_py(int64_t K, int64_t N) {
+  WgradGemvPlan plan;
+  if (!wgrad_gemv_plan(K, N, &plan)) return {0, 0};
+  return {plan.use ? 1 : 0, plan.num_chunks};
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -1633,4 +1668,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("tile") = -1);
   m.def("wgrad_splitk_plan", &wgrad_splitk_plan_py,
         "(use, splitk, tile geometry) for g [K, M], x [K, N]");
+  m.def("wgrad_gemv", &wgrad_gemv,
+        "Linear(N, 1) weight and bias gradient -> (gw [1, N], gb [1]) (gfx950)",
+        pybind11::arg("g"), pybind11::arg("x"));
+  m.def("wgrad_gemv_plan", &wgrad_gemv_plan_py,
+        "(use, row chunks) for g [K, 1], x [K, N]");
 }

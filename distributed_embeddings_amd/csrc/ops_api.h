@@ -308,6 +308,21 @@ void launch_wgrad_splitk(const void* g, const void* x, float* slab, void* gw,
                          int64_t K, int M, int N, const WgradSplitkPlan& plan,
                          hipStream_t stream);
 
+// wgrad_splitk.hip.  The same for a Linear with one output feature, with its
+// bias gradient: gw [N] = bf16(sum_k g[k] x[k, n]), gb [1] = bf16(sum_k g[k])
+// for bf16 g [K] and x [K, N], N % 8 == 0, x 16-byte aligned.  Partial sums
+// into the fp32 slab [num_chunks, N + 1], then a fixed-order sum.
+struct WgradGemvPlan {
+  int64_t rows_per_chunk;
+  int64_t num_chunks;  // <= 1024
+  bool use;            // route the MLP's final layer of this shape here
+};
+// false: the kernels do not take this shape
+bool wgrad_gemv_plan(int64_t K, int64_t N, WgradGemvPlan* plan);
+void launch_wgrad_gemv(const void* g, const void* x, float* slab, void* gw,
+                       void* gb, int64_t K, int N, const WgradGemvPlan& plan,
+                       hipStream_t stream);
+
 size_t custom_radix_sort_hist_elems(int64_t n);
 int custom_radix_sort_num_variants();
 // keys per block of tile geometry `variant` in [0, num_variants)

@@ -30,6 +30,9 @@
 //
 // Rows of x that are no multiple of 16 B (the 13 numerical features) are
 // staged element by element into a zero-padded 16-column tile (NARROW).
+//
+// wgrad_gemv: the M = 1 case (the final Linear(., 1)), with its bias gradient,
+// as a streaming kernel without MFMA; described where it stands below.
 
 #include <hip/hip_runtime.h>
 
@@ -277,7 +280,174 @@ void launch_partial(const void* g, const void* x, float* slab, int64_t K,
       (const short*)g, (const short*)x, slab, K, M, N, Np, kslice, tiles_n);
 }
 
+// ---------------------------------------------------------------------------
+// wgrad_gemv: the weight and bias gradient of a Linear with ONE output
+// feature, gw[n] = bf16(sum_k g[k] x[k, n]) and gb = bf16(sum_k g[k]) for
+// g [K] and x [K, N], N % 8 == 0.  No MFMA: one multiply-add per element
+// loaded, so the kernel streams x in the manner of relu_bwd_bias_partial
+// (mlp_ops.hip).  Block = GV_COLS x GV_ROWS threads, a lane owns 8 adjacent
+// columns (one 16-B load per row) and walks its row chunk GV_ROWS rows at a
+// time with GV_UNROLL loads in flight.  grid = (column tiles, row chunks).
+// Every block writes one fp32 row of slab [chunks][N + 1] with plain stores
+// (column N: the chunk's sum of g, from the blocks of column tile 0);
+// wgrad_gemv_finish sums the rows in a fixed order.
+// ---------------------------------------------------------------------------
+constexpr int GV_COLS = 32;
+constexpr int GV_ROWS = 8;
+constexpr int GV_TILE_N = GV_COLS * 8;
+constexpr int GV_UNROLL = 4;
+
+__device__ __forceinline__ float bf16_bits_to_f32(unsigned short h) {
+  return __uint_as_float((unsigned int)h << 16);
+}
+
+typedef __attribute__((ext_vector_type(8))) unsigned short u16x8;
+
+// Scalar fp32 arithmetic for the device pass: without it the 8 multiply-adds
+// of a row become v_pk_fma_f32 with a broadcast operand, a form this project
+// does not rely on; the kernel is bound by its loads either way.  (The host
+// pass does not know the feature and would warn.)
+#if defined(__HIP_DEVICE_COMPILE__)
+#define DE_NO_PACKED_FP32 __attribute__((target("no-packed-fp32-ops")))
+#else
+#define DE_NO_PACKED_FP32
+#endif
+
+DE_NO_PACKED_FP32 __global__ __launch_bounds__(GV_COLS* GV_ROWS) void wgrad_gemv_partial(
+    const unsigned short* __restrict__ g, const unsigned short* __restrict__ x,
+    float* __restrict__ slab, int64_t K, int N, int64_t rows_per_chunk) {
+  __shared__ float part[GV_ROWS][GV_TILE_N + 4];
+  __shared__ float gpart[GV_ROWS];
+  const int cl = threadIdx.x % GV_COLS;
+  const int rl = threadIdx.x / GV_COLS;
+  const int col = blockIdx.x * GV_TILE_N + cl * 8;  // N % 8 == 0: all 8 or none
+  const int64_t r0 = (int64_t)blockIdx.y * rows_per_chunk;
+  int64_t r1 = r0 + rows_per_chunk;
+  if (r1 > K) r1 = K;
+
+  float acc[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) acc[j] = 0.f;
+  float gsum = 0.f;
+
+  if (col < N) {
+    for (int64_t r = r0 + rl; r < r1; r += GV_ROWS * GV_UNROLL) {
+      u16x8 xv[GV_UNROLL];
+      unsigned short gv[GV_UNROLL];
+#pragma unroll
+      for (int u = 0; u < GV_UNROLL; ++u) {
+        const int64_t ru = r + u * GV_ROWS;
+        if (ru < r1) {
+          xv[u] = *reinterpret_cast<const u16x8*>(x + ru * N + col);
+          gv[u] = g[ru];
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < GV_UNROLL; ++u) {
+        const int64_t ru = r + u * GV_ROWS;
+        if (ru < r1) {
+          const float gf = bf16_bits_to_f32(gv[u]);
+          gsum += gf;
+          // the product of two bf16 is exact in fp32: contraction to an fma
+          // changes nothing
+#pragma unroll
+          for (int j = 0; j < 8; ++j) acc[j] += gf * bf16_bits_to_f32(xv[u][j]);
+        }
+      }
+    }
+  }
+
+#pragma unroll
+  for (int j = 0; j < 8; ++j) part[rl][cl * 8 + j] = acc[j];
+  if (cl == 0) gpart[rl] = gsum;
+  __syncthreads();
+  float* out = slab + (int64_t)blockIdx.y * (N + 1);
+  const int c = blockIdx.x * GV_TILE_N + threadIdx.x;
+  if (c < N) {
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < GV_ROWS; ++i) s += part[i][threadIdx.x];
+    out[c] = s;
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < GV_ROWS; ++i) s += gpart[i];
+    out[N] = s;
+  }
+}
+
+// gw[n] = bf16(sum_r slab[r][n]) for n < N, gb = bf16(sum_r slab[r][N]).
+// Block = 32 columns x 32 row groups; group i sums rows i, i+32, ... in
+// order, then the 32 partial sums in order.
+constexpr int GVF_COLS = 32;
+constexpr int GVF_GROUPS = 32;
+
+__global__ __launch_bounds__(GVF_COLS* GVF_GROUPS) void wgrad_gemv_finish(
+    const float* __restrict__ slab, unsigned short* __restrict__ gw,
+    unsigned short* __restrict__ gb, int R, int N) {
+  __shared__ float part[GVF_GROUPS][GVF_COLS + 1];
+  const int c = threadIdx.x % GVF_COLS;
+  const int grp = threadIdx.x / GVF_COLS;
+  const int col = blockIdx.x * GVF_COLS + c;
+  float s = 0.f;
+  if (col <= N) {
+#pragma unroll 4
+    for (int r = grp; r < R; r += GVF_GROUPS) {
+      s += slab[(int64_t)r * (N + 1) + col];
+    }
+  }
+  part[grp][c] = s;
+  __syncthreads();
+  if (grp == 0 && col <= N) {
+    float t = 0.f;
+#pragma unroll
+    for (int i = 0; i < GVF_GROUPS; ++i) t += part[i][c];
+    if (col < N) {
+      gw[col] = f32_to_bf16_rne(t);
+    } else {
+      gb[0] = f32_to_bf16_rne(t);
+    }
+  }
+}
+
 }  // namespace
+
+bool wgrad_gemv_plan(int64_t K, int64_t N, WgradGemvPlan* plan) {
+  if (K < 1 || N < 8 || N % 8 != 0 || N >= (1 << 24)) return false;
+  // a few thousand blocks at the flagship shape; slab <= 1024 rows
+  const int64_t col_tiles = (N + GV_TILE_N - 1) / GV_TILE_N;
+  int64_t r = 2048 / col_tiles;
+  if (r > 1024) r = 1024;
+  if (r < 1) r = 1;
+  int64_t rpc = (K + r - 1) / r;
+  constexpr int STEP = GV_ROWS * GV_UNROLL;
+  rpc = (rpc + STEP - 1) / STEP * STEP;
+  plan->rows_per_chunk = rpc;
+  plan->num_chunks = (K + rpc - 1) / rpc;
+  // Routing: measured ahead of the library's GEMM + column sum at N = 256
+  // from K = 4096 (8.5 against 26 us) to 65536 (12.8 against 90 us,
+  // profiles/wgrad_tiles.md); 8192 is the smallest K measured above the
+  // small batches that stay on the library.
+  plan->use = K >= 8192;
+  return true;
+}
+
+void launch_wgrad_gemv(const void* g, const void* x, float* slab, void* gw,
+                       void* gb, int64_t K, int N, const WgradGemvPlan& plan,
+                       hipStream_t stream) {
+  const int col_tiles = (N + GV_TILE_N - 1) / GV_TILE_N;
+  hipLaunchKernelGGL(wgrad_gemv_partial,
+                     dim3(col_tiles, (unsigned)plan.num_chunks),
+                     dim3(GV_COLS * GV_ROWS), 0, stream,
+                     (const unsigned short*)g, (const unsigned short*)x, slab,
+                     K, N, plan.rows_per_chunk);
+  hipLaunchKernelGGL(wgrad_gemv_finish,
+                     dim3((N + 1 + GVF_COLS - 1) / GVF_COLS),
+                     dim3(GVF_COLS * GVF_GROUPS), 0, stream,
+                     (const float*)slab, (unsigned short*)gw,
+                     (unsigned short*)gb, (int)plan.num_chunks, N);
+}
 
 bool wgrad_splitk_plan(int64_t K, int64_t M, int64_t N, WgradSplitkPlan* plan) {
   return wgrad_splitk_plan_with(K, M, N, 0, -1, plan);

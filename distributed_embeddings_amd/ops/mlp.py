@@ -9,7 +9,9 @@ names and every GEMM call of that path and replaces the two passes by one
 
 The weight gradient ``g.t().mm(x)``, summed over the batch, goes to the
 split-K kernels of ``csrc/wgrad_splitk.hip`` at the shapes their plan routes
-(``weight_grad``).
+(``weight_grad``).  A closing ``Linear`` with one output feature (the logit
+layer) gets its weight and bias gradient from one streaming pass
+(``final_layer_grads``).
 
 ``DE_FUSED_MLP=0`` switches the fast path off (plain ``nn.Sequential``);
 ``DE_WGRAD_SPLITK=0`` keeps the weight gradients on the GEMM library.
@@ -95,13 +97,66 @@ class _LinearReLU(torch.autograd.Function):
         return gx, gw, gb
 
 
+def _wgrad_gemv_routed(k: int, n: int) -> bool:
+    """Whether the plan (``wgrad_gemv_plan``) sends this shape to the kernel."""
+    return bool(_backend.ops().wgrad_gemv_plan(k, n)[0])
+
+
+def final_layer_grads(g: torch.Tensor,
+                      xb: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``(g.t().mm(xb), g.sum(0))`` for ``g [K, 1]``: one streaming pass
+    (``wgrad_gemv``, ``csrc/wgrad_splitk.hip``) under the guards of
+    ``weight_grad``, the library for everything else.
+    """
+    if (g.is_cuda and g.dim() == 2 and xb.dim() == 2 and g.shape[1] == 1
+            and g.dtype == torch.bfloat16 and xb.dtype == torch.bfloat16
+            and g.is_contiguous() and xb.is_contiguous()
+            and xb.data_ptr() % 16 == 0
+            and os.environ.get("DE_WGRAD_SPLITK", "1") != "0"
+            and _wgrad_gemv_routed(g.shape[0], xb.shape[1])):
+        gw, gb = _backend.ops().wgrad_gemv(g, xb)
+        return gw, gb
+    return g.t().mm(xb), g.sum(0)
+
+
+class _LinearOut1(torch.autograd.Function):
+    """``addmm(b, x, W^T)`` in bf16 for an fp32 ``Linear`` with one output
+    feature and no ReLU behind it (the logit layer).
+
+    Issues exactly the casts and GEMM calls of autocast ``F.linear`` and of
+    its autograd backward, except that the weight gradient ``g.t().mm(x)``
+    and the bias gradient ``g.sum(0)``, two passes with ``M = 1`` that the
+    library runs on a handful of workgroups, come from ``final_layer_grads``.
+    """
+
+    @staticmethod
+    def forward(ctx, x, w, b):
+        xb = x.to(torch.bfloat16)
+        wb = w.to(torch.bfloat16)
+        y = torch.addmm(b.to(torch.bfloat16), xb, wb.t())
+        ctx.save_for_backward(xb, wb)
+        ctx.x_dtype = x.dtype
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        xb, wb = ctx.saved_tensors
+        gx = None
+        if ctx.needs_input_grad[0]:
+            gx = grad_out.mm(wb).to(ctx.x_dtype)
+        gw, gb = final_layer_grads(grad_out, xb)
+        return gx, gw, gb
+
+
 class MLP(nn.Sequential):
     """``nn.Sequential`` of ``Linear`` and ``ReLU`` with a fused GPU path.
 
     Same children, parameter names and ``state_dict`` as the plain
     ``nn.Sequential``.  For a 2-D GPU input under bf16 autocast, with the HIP
     extension built, every ``Linear`` (fp32, with bias) followed by a
-    ``ReLU`` runs as one ``_LinearReLU``; every other module runs as it is.
+    ``ReLU`` runs as one ``_LinearReLU``, such a ``Linear`` with one output
+    feature and no ``ReLU`` as ``_LinearOut1``; every other module runs as it is.
     Everything else takes the unchanged ``nn.Sequential`` forward.
     """
 
@@ -119,13 +174,15 @@ class MLP(nn.Sequential):
         i = 0
         while i < len(mods):
             m = mods[i]
-            if (isinstance(m, nn.Linear) and m.bias is not None
+            ours = (isinstance(m, nn.Linear) and m.bias is not None
                     and m.weight.dtype == torch.float32
-                    and m.bias.dtype == torch.float32
-                    and i + 1 < len(mods) and isinstance(mods[i + 1], nn.ReLU)
-                    and h.dim() == 2):
+                    and m.bias.dtype == torch.float32 and h.dim() == 2)
+            if ours and i + 1 < len(mods) and isinstance(mods[i + 1], nn.ReLU):
                 h = _LinearReLU.apply(h, m.weight, m.bias)
                 i += 2
+            elif ours and m.out_features == 1:
+                h = _LinearOut1.apply(h, m.weight, m.bias)
+                i += 1
             else:
                 h = m(h)
                 i += 1

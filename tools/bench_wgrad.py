@@ -16,14 +16,24 @@ device events, with the rounds' min and max.  Two operand-residency modes:
 One JSON line per (shape, mode, method).  `tb_s` counts the operand bytes
 only (the slab is overhead), `tflop_s` the 2 K M N flops.
 
+A shape with M = 1 (`1x256`, the logit layer; not among the defaults' seven)
+times `wgrad_gemv`, which also gives the bias gradient, against `gemm`
+(`g.t().mm(x)` alone) and `gemm+sum` (with the `g.sum(0)` it replaces too).
+
   python tools/bench_wgrad.py
   python tools/bench_wgrad.py --shapes 256x512 128x256 --splitk 8 16 32 --tile 0 1
   python tools/bench_wgrad.py --modes rotate --k 32768
+  python tools/bench_wgrad.py --shapes 1x256 --k 4096 16384 65536
+  python tools/bench_wgrad.py --ext OTHER/_hip_ops*.so
+
+--ext times another build of the extension (e.g. the parent commit's) on the
+same machine in the same kind of process.
 
 --splitk / --tile time the kernel with those settings too (0 / -1: the
 plan's own), for choosing the plan.
 """
 import argparse
+import importlib.util
 import json
 import os
 import statistics
@@ -54,9 +64,20 @@ def enable_tunableop():
     return [os.path.basename(c) for c in csvs]
 
 
+def load_ext(path):
+    if path is None:
+        from distributed_embeddings_amd.ops import _backend
+        return _backend.ops()
+    spec = importlib.util.spec_from_file_location("_hip_ops", path)
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
 def main():
     p = argparse.ArgumentParser()
-    p.add_argument("--k", type=int, default=65536)
+    p.add_argument("--ext", default=None)
+    p.add_argument("--k", nargs="+", type=int, default=[65536])
     p.add_argument("--shapes", nargs="+", default=None, metavar="MxN")
     p.add_argument("--modes", nargs="+", default=["same", "rotate"],
                    choices=["same", "rotate"])
@@ -66,28 +87,33 @@ def main():
     p.add_argument("--iters", type=int, default=20)
     args = p.parse_args()
     assert torch.cuda.is_available(), "needs a GPU: no timing without one"
-    from distributed_embeddings_amd.ops import _backend
-    ext = _backend.ops()
+    ext = load_ext(args.ext)
     csvs = enable_tunableop()
 
     shapes = SHAPES
     if args.shapes:
         shapes = [tuple(int(v) for v in s.split("x")) for s in args.shapes]
-    k = args.k
     torch.manual_seed(0)
     done = set()
-    for m, n in shapes:
-        if (m, n) in done:
+    for k, m, n in [(k, m, n) for k in args.k for m, n in shapes]:
+        if (k, m, n) in done:
             continue
-        done.add((m, n))
+        done.add((k, m, n))
         pair_bytes = k * (m + n) * 2
         variants = [("gemm", 0, -1)]
-        for t in args.tile:
-            if t == 2 and n > 16 or t in (0, 1) and n % 8 != 0:
-                continue
-            for s in args.splitk:
-                variants.append(("wgrad_splitk", s, t))
-        plan = ext.wgrad_splitk_plan(k, m, n)
+        if m == 1:
+            variants.append(("gemm+sum", 0, -1))
+            if hasattr(ext, "wgrad_gemv"):
+                variants.append(("wgrad_gemv", 0, -1))
+            plan = ext.wgrad_gemv_plan(k, n) \
+                if hasattr(ext, "wgrad_gemv_plan") else []
+        else:
+            for t in args.tile:
+                if t == 2 and n > 16 or t in (0, 1) and n % 8 != 0:
+                    continue
+                for s in args.splitk:
+                    variants.append(("wgrad_splitk", s, t))
+            plan = ext.wgrad_splitk_plan(k, m, n)
         for mode in args.modes:
             npairs = 1 if mode == "same" else \
                 max(2, -(-3 * INFINITY_CACHE // pair_bytes))
@@ -99,6 +125,10 @@ def main():
                 g, x = pool[i % npairs]
                 if v[0] == "gemm":
                     return g.t().mm(x)
+                if v[0] == "gemm+sum":
+                    return g.t().mm(x), g.sum(0)
+                if v[0] == "wgrad_gemv":
+                    return ext.wgrad_gemv(g, x)
                 return ext.wgrad_splitk(g, x, v[1], v[2])
 
             for v in variants:
@@ -128,7 +158,7 @@ def main():
                     "operand_mb": round(pair_bytes / 1e6, 1),
                     "tb_s": round(pair_bytes / med / 1e6, 2),
                     "tflop_s": round(2.0 * k * m * n / med / 1e6, 1),
-                    "tunableop": csvs,
+                    "tunableop": csvs, "ext": args.ext or "in-tree",
                 }), flush=True)
             del pool
             torch.cuda.empty_cache()
