@@ -1269,6 +1269,120 @@ std::vector<torch::Tensor> dot_interact_narrow_bwd_packed(torch::Tensor gout,
   return {gbottom, gpacked};
 }
 
+// fp32 inputs (dot_interact_f32.hip): 1 <= F <= 32, D % 8 == 0, 8 <= D <= 256,
+// fp32 in and out.  Feature rows move as 16-B vectors, so the feature tensors
+// must start on a 16-B boundary; out / gout rows are 4-byte aligned.  perm as
+// for the narrow bindings.
+static void check_dot_interact_f32_shape(int64_t F, int64_t D) {
+  TORCH_CHECK(F >= 1 && F <= 32 && D >= 8 && D <= 256 && D % 8 == 0,
+              "1 <= F <= 32, D % 8 == 0 and 8 <= D <= 256 required (got F=", F,
+              ", D=", D, ")");
+}
+
+static void check_f32(const torch::Tensor& t, const char* name) {
+  CHECK_CUDA(t); CHECK_CONTIG(t);
+  TORCH_CHECK(t.dtype() == torch::kFloat32, name, " must be float32");
+}
+
+// (F, D, sb, sp) of a checked (bottom, packed, perm) triple
+struct F32Packed {
+  int64_t B, sb, sp;
+  int F, D, tri_n;
+};
+
+static F32Packed check_f32_packed(const torch::Tensor& bottom,
+                                  const torch::Tensor& packed,
+                                  const torch::Tensor& perm,
+                                  bool sample_major) {
+  check_f32(bottom, "bottom");
+  check_f32(packed, "packed");
+  CHECK_CUDA(perm); CHECK_CONTIG(perm);
+  TORCH_CHECK(perm.dtype() == torch::kInt32, "perm must be int32");
+  TORCH_CHECK(packed.device() == bottom.device() &&
+              perm.device() == bottom.device(), "tensors on one device");
+  TORCH_CHECK(bottom.dim() == 2 && packed.dim() == 3, "bottom [B,D], packed 3-D");
+  const int64_t B = bottom.size(0), D = bottom.size(1);
+  const int64_t P = sample_major ? packed.size(1) : packed.size(0);
+  TORCH_CHECK(packed.size(sample_major ? 0 : 1) == B && packed.size(2) == D,
+              "shape mismatch");
+  TORCH_CHECK(perm.numel() == P, "perm must have P entries");
+  check_dot_interact_f32_shape(P + 1, D);
+  check_align16(bottom, "bottom");
+  check_align16(packed, "packed");
+  const int F = (int)P + 1;
+  return {B, sample_major ? P : 1, sample_major ? 1 : B, F, (int)D,
+          F * (F - 1) / 2};
+}
+
+torch::Tensor dot_interact_f32_fwd(torch::Tensor feats, int64_t out_w) {
+  check_f32(feats, "feats");
+  TORCH_CHECK(feats.dim() == 3, "feats must be [B, F, D]");
+  check_dot_interact_f32_shape(feats.size(1), feats.size(2));
+  check_align16(feats, "feats");
+  const int64_t B = feats.size(0);
+  const int F = (int)feats.size(1), D = (int)feats.size(2);
+  const int tri_n = F * (F - 1) / 2;
+  TORCH_CHECK(out_w >= tri_n + D && out_w <= INT32_MAX, "out width too small");
+  auto out = torch::empty({B, out_w}, feats.options());
+  launch_dot_interact_f32_fwd(feats.data_ptr(), out.data_ptr(), B, F, D,
+                              (int)out_w, tri_n, current_stream());
+  return out;
+}
+
+torch::Tensor dot_interact_f32_bwd(torch::Tensor gout, torch::Tensor feats) {
+  check_f32(gout, "gout");
+  check_f32(feats, "feats");
+  TORCH_CHECK(gout.device() == feats.device(), "tensors on one device");
+  TORCH_CHECK(gout.dim() == 2 && feats.dim() == 3, "gout [B,W], feats [B,F,D]");
+  check_dot_interact_f32_shape(feats.size(1), feats.size(2));
+  check_align16(feats, "feats");
+  const int64_t B = feats.size(0);
+  const int F = (int)feats.size(1), D = (int)feats.size(2);
+  const int tri_n = F * (F - 1) / 2;
+  TORCH_CHECK(gout.size(0) == B && gout.size(1) >= tri_n + D &&
+              gout.size(1) <= INT32_MAX, "gout must be [B, >= F(F-1)/2 + D]");
+  auto gfeats = torch::empty_like(feats);
+  launch_dot_interact_f32_bwd(gout.data_ptr(), feats.data_ptr(),
+                              gfeats.data_ptr(), B, F, D, (int)gout.size(1),
+                              tri_n, current_stream());
+  return gfeats;
+}
+
+torch::Tensor dot_interact_f32_fwd_packed(torch::Tensor bottom,
+                                          torch::Tensor packed,
+                                          torch::Tensor perm, int64_t out_w,
+                                          bool sample_major) {
+  const F32Packed s = check_f32_packed(bottom, packed, perm, sample_major);
+  TORCH_CHECK(out_w >= s.tri_n + s.D && out_w <= INT32_MAX,
+              "out width too small");
+  auto out = torch::empty({s.B, out_w}, bottom.options());
+  launch_dot_interact_f32_fwd_packed(
+      bottom.data_ptr(), packed.data_ptr(), perm.data_ptr<int>(),
+      out.data_ptr(), s.B, s.F, s.D, (int)out_w, s.tri_n, s.sb, s.sp,
+      current_stream());
+  return out;
+}
+
+std::vector<torch::Tensor> dot_interact_f32_bwd_packed(torch::Tensor gout,
+                                                       torch::Tensor bottom,
+                                                       torch::Tensor packed,
+                                                       torch::Tensor perm,
+                                                       bool sample_major) {
+  check_f32(gout, "gout");
+  const F32Packed s = check_f32_packed(bottom, packed, perm, sample_major);
+  TORCH_CHECK(gout.device() == bottom.device(), "tensors on one device");
+  TORCH_CHECK(gout.dim() == 2 && gout.size(0) == s.B &&
+              gout.size(1) >= s.tri_n + s.D && gout.size(1) <= INT32_MAX,
+              "gout must be [B, >= F(F-1)/2 + D]");
+  auto gbottom = torch::empty_like(bottom);
+  auto gpacked = torch::empty_like(packed);
+  launch_dot_interact_f32_bwd_packed(
+      gout.data_ptr(), bottom.data_ptr(), packed.data_ptr(),
+      perm.data_ptr<int>(), gbottom.data_ptr(), gpacked.data_ptr(), s.B, s.F,
+      s.D, (int)gout.size(1), s.tri_n, s.sb, s.sp, current_stream());
+  return {gbottom, gpacked};
+}
+
 // ReLU backward fused with the bias gradient: one pass over grad_out and y
 // (mlp_ops.hip).  Outputs and the fp32 partial slab come from the torch
 // allocator, so the op can be captured in a hipGraph.
@@ -1646,6 +1760,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "narrow interaction on (bottom, packed, perm) (MFMA, gfx950)");
   m.def("dot_interact_narrow_bwd_packed", &dot_interact_narrow_bwd_packed,
         "narrow packed interaction backward -> (gbottom, gpacked) (gfx950)");
+  m.def("dot_interact_f32_fwd", &dot_interact_f32_fwd,
+        "interaction forward on fp32, F <= 32, D % 8 == 0 (MFMA f32, gfx950)");
+  m.def("dot_interact_f32_bwd", &dot_interact_f32_bwd,
+        "interaction backward on fp32, F <= 32, D % 8 == 0 (MFMA f32, gfx950)");
+  m.def("dot_interact_f32_fwd_packed", &dot_interact_f32_fwd_packed,
+        "fp32 interaction on (bottom, packed, perm) (MFMA f32, gfx950)");
+  m.def("dot_interact_f32_bwd_packed", &dot_interact_f32_bwd_packed,
+        "fp32 packed interaction backward -> (gbottom, gpacked) (gfx950)");
   m.def("relu_bwd_bias_grad", &relu_bwd_bias_grad,
         "ReLU backward + bias gradient in one pass -> (grad_in, bias_grad) "
         "(gfx950)");

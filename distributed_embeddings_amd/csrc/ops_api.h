@@ -252,6 +252,26 @@ void launch_dot_interact_fwd_narrow(const void* feats, void* out, int64_t B,
 void launch_dot_interact_bwd_narrow(const void* gout, const void* feats,
                                     void* gfeats, int64_t B, int F, int D,
                                     int out_w, int tri_n, hipStream_t stream);
+// dot_interact_f32.hip.  fp32 in and out: 1 <= F <= 32, D % 8 == 0,
+// 8 <= D <= 256, the same arguments and layouts as the narrow launchers;
+// std::invalid_argument outside that.  Feature rows must be 16-byte aligned.
+void launch_dot_interact_f32_fwd_packed(const void* bottom, const void* packed,
+                                        const int* perm, void* out, int64_t B,
+                                        int F, int D, int out_w, int tri_n,
+                                        int64_t sb, int64_t sp,
+                                        hipStream_t stream);
+void launch_dot_interact_f32_bwd_packed(const void* gout, const void* bottom,
+                                        const void* packed, const int* perm,
+                                        void* gbottom, void* gpacked, int64_t B,
+                                        int F, int D, int out_w, int tri_n,
+                                        int64_t sb, int64_t sp,
+                                        hipStream_t stream);
+void launch_dot_interact_f32_fwd(const void* feats, void* out, int64_t B,
+                                 int F, int D, int out_w, int tri_n,
+                                 hipStream_t stream);
+void launch_dot_interact_f32_bwd(const void* gout, const void* feats,
+                                 void* gfeats, int64_t B, int F, int D,
+                                 int out_w, int tri_n, hipStream_t stream);
 
 // mlp_ops.hip.  relu_bwd_bias_grad: grad_in = (y <= 0) ? 0 : grad_out and
 // bias_grad = bf16(column sums of grad_in), bf16 [B, N] with N % 8 == 0.

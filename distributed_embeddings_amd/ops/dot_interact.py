@@ -3,10 +3,13 @@
 Replaces the stack + bmm + tril-mask + concat chain of the reference
 (``examples/dlrm/utils.py:92-113``) with one MFMA kernel each direction
 (``csrc/dot_interact.hip``).  Falls back to plain torch ops off-GPU, for
-inputs that are not bf16, and for shapes the kernels do not take: they need
-D % 32 == 0 and either F <= 32, or F <= 64 with D <= 256 (F counts the
-bottom-MLP output as feature 0).  D = 8, 16 and 24 with F <= 32 run the narrow
-kernels (``narrow_shape_ok``); ``DE_DI_NARROW=0`` sends them to the torch ops.
+inputs that are neither all bf16 nor all fp32, and for shapes the kernels do
+not take.  The bf16 kernels need D % 32 == 0 and either F <= 32, or F <= 64
+with D <= 256 (F counts the bottom-MLP output as feature 0).  D = 8, 16 and 24
+with F <= 32 run the narrow kernels (``narrow_shape_ok``); ``DE_DI_NARROW=0``
+sends them to the torch ops.  fp32 inputs with F <= 32, D % 8 == 0 and
+8 <= D <= 256 run the fp32 MFMA kernels of ``csrc/dot_interact_f32.hip``
+(``f32_shape_ok``); ``DE_DI_F32=0`` sends them to the torch ops.
 """
 
 import os
@@ -31,6 +34,15 @@ def narrow_shape_ok(f: int, d: int) -> bool:
 
 def _use_narrow(f: int, d: int) -> bool:
     return narrow_shape_ok(f, d) and os.environ.get("DE_DI_NARROW", "1") != "0"
+
+
+def f32_shape_ok(f: int, d: int) -> bool:
+    """Whether the fp32 HIP kernels take ``f`` features of width ``d``."""
+    return 1 <= f <= 32 and d % 8 == 0 and 8 <= d <= 256
+
+
+def _use_f32(f: int, d: int) -> bool:
+    return f32_shape_ok(f, d) and os.environ.get("DE_DI_F32", "1") != "0"
 
 
 def _aligned16(t: torch.Tensor) -> torch.Tensor:
@@ -63,6 +75,19 @@ class _DotInteractNarrow(torch.autograd.Function):
     def backward(ctx, gout):
         (feats,) = ctx.saved_tensors
         gfeats = _backend.ops().dot_interact_narrow_bwd(gout.contiguous(), feats)
+        return gfeats, None
+
+
+class _DotInteractF32(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, feats, out_w):
+        ctx.save_for_backward(feats)
+        return _backend.ops().dot_interact_f32_fwd(feats, out_w)
+
+    @staticmethod
+    def backward(ctx, gout):
+        (feats,) = ctx.saved_tensors
+        gfeats = _backend.ops().dot_interact_f32_bwd(gout.contiguous(), feats)
         return gfeats, None
 
 
@@ -111,6 +136,22 @@ class _DotInteractNarrowPacked(torch.autograd.Function):
         return gbottom, gpacked, None, None, None
 
 
+class _DotInteractF32Packed(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, bottom, packed, perm, out_w, sample_major):
+        ctx.save_for_backward(bottom, packed, perm)
+        ctx.sample_major = sample_major
+        return _backend.ops().dot_interact_f32_fwd_packed(
+            bottom, packed, perm, out_w, sample_major)
+
+    @staticmethod
+    def backward(ctx, gout):
+        bottom, packed, perm = ctx.saved_tensors
+        gbottom, gpacked = _backend.ops().dot_interact_f32_bwd_packed(
+            gout.contiguous(), bottom, packed, perm, ctx.sample_major)
+        return gbottom, gpacked, None, None, None
+
+
 def dot_interact_packed(packed: torch.Tensor, bottom_mlp_out: torch.Tensor,
                         perm: torch.Tensor, pad_to: int = 0,
                         sample_major: bool = False) -> torch.Tensor:
@@ -139,6 +180,14 @@ def dot_interact_packed(packed: torch.Tensor, bottom_mlp_out: torch.Tensor,
             return _DotInteractNarrowPacked.apply(
                 _aligned16(bottom_mlp_out), _aligned16(packed), perm, out_w,
                 sample_major)
+    if (packed.is_cuda and bottom_mlp_out.is_cuda
+            and packed.dtype == torch.float32
+            and bottom_mlp_out.dtype == torch.float32
+            and perm.is_cuda and perm.dtype == torch.int32
+            and _use_f32(f, d)):
+        return _DotInteractF32Packed.apply(
+            _aligned16(bottom_mlp_out), _aligned16(packed), perm.contiguous(),
+            out_w, sample_major)
     # fallback (CPU / unsupported shapes): materialize [B, F, D] and reuse
     # the plain path
     sel = packed.index_select(1, perm.long()) if sample_major else \
@@ -159,4 +208,6 @@ def dot_interact(emb_outs: List[torch.Tensor], bottom_mlp_out: torch.Tensor,
             return _DotInteract.apply(feats.contiguous(), out_w)
         if _use_narrow(f, d):
             return _DotInteractNarrow.apply(_aligned16(feats), out_w)
+    if feats.is_cuda and feats.dtype == torch.float32 and _use_f32(f, d):
+        return _DotInteractF32.apply(_aligned16(feats), out_w)
     return _torch_dot_interact(feats, out_w)

@@ -14,6 +14,8 @@ over rounds of the mean call time, taken with device events.
   python tools/bench_interact.py --features 40 --only torch  # the torch fallback
   python tools/bench_interact.py --dim 16 --only op   # the public op (narrow kernels)
   DE_DI_NARROW=0 python tools/bench_interact.py --dim 16 --only op  # its fallback
+  python tools/bench_interact.py --dtype fp32 --only op   # the fp32 MFMA kernels
+  DE_DI_F32=0 python tools/bench_interact.py --dtype fp32 --only op  # their fallback
 
 --ext times another build of the extension (e.g. the parent commit's) on the
 same inputs; run the two builds in alternating processes.
@@ -110,6 +112,9 @@ def main():
     p.add_argument("--width", "--dim", type=int, default=128,
                    help="D: a multiple of 32, or 8, 16, 24 (with --only op "
                         "or torch: the raw packed bindings reject those)")
+    p.add_argument("--dtype", choices=("bf16", "fp32"), default="bf16",
+                   help="fp32: D a multiple of 8, 8..256; the raw bindings timed are "
+                        "then the dot_interact_f32_* ones")
     p.add_argument("--sample-major", action="store_true",
                    help="packed block as [B, P, D] (the world==1 layout)")
     p.add_argument("--rounds", type=int, default=7)
@@ -125,35 +130,39 @@ def main():
     P = F - 1
     out_w = (F * P // 2 + D + 63) // 64 * 64
     # bytes the result needs: features (+ gout) read, out or gradients written
-    gb_fwd = B * (F * D + out_w) * 2 / 1e9
-    gb_bwd = B * (2 * F * D + out_w) * 2 / 1e9
+    fp32 = args.dtype == "fp32"
+    dt = torch.float32 if fp32 else torch.bfloat16
+    gb_fwd = B * (F * D + out_w) * dt.itemsize / 1e9
+    gb_bwd = B * (2 * F * D + out_w) * dt.itemsize / 1e9
     sm = args.sample_major
-    packed = torch.randn((B, P, D) if sm else (P, B, D), device="cuda").bfloat16()
-    bottom = torch.randn(B, D, device="cuda").bfloat16()
+    packed = torch.randn((B, P, D) if sm else (P, B, D), device="cuda").to(dt)
+    bottom = torch.randn(B, D, device="cuda").to(dt)
     perm = torch.arange(P, dtype=torch.int32, device="cuda")
-    gout = torch.randn(B, out_w, device="cuda").bfloat16()
+    gout = torch.randn(B, out_w, device="cuda").to(dt)
     tag = "samp-major" if sm else "feat-major"
     print(f"B={B} F={F} D={D} out_w={out_w}")
     if args.only in ("torch", "op"):
         runs = torch_runs(packed, bottom, perm, gout, out_w, sm, tag,
                           gb_fwd, gb_bwd, public_op=args.only == "op")
         print("ext: none (torch ops)" if args.only == "torch" else
-              f"public op, DE_DI_NARROW={os.environ.get('DE_DI_NARROW', '1')}")
+              f"public op, DE_DI_NARROW={os.environ.get('DE_DI_NARROW', '1')}"
+              f" DE_DI_F32={os.environ.get('DE_DI_F32', '1')}")
     else:
         ext = load_ext(args.ext)
+        pre = "dot_interact_f32_" if fp32 else "dot_interact_"
+        fwd_p, bwd_p = getattr(ext, pre + "fwd_packed"), getattr(ext, pre + "bwd_packed")
+        fwd_s, bwd_s = getattr(ext, pre + "fwd"), getattr(ext, pre + "bwd")
         runs = [
             (f"fwd  packed {tag}", gb_fwd,
-             lambda: ext.dot_interact_fwd_packed(bottom, packed, perm, out_w, sm)),
+             lambda: fwd_p(bottom, packed, perm, out_w, sm)),
             (f"bwd  packed {tag}", gb_bwd,
-             lambda: ext.dot_interact_bwd_packed(gout, bottom, packed, perm, sm)),
+             lambda: bwd_p(gout, bottom, packed, perm, sm)),
         ]
         if args.only == "all":
-            feats = torch.randn(B, F, D, device="cuda").bfloat16()
+            feats = torch.randn(B, F, D, device="cuda").to(dt)
             runs = [
-                ("fwd  old [B,F,D]      ", gb_fwd,
-                 lambda: ext.dot_interact_fwd(feats, out_w)),
-                ("bwd  old [B,F,D]      ", gb_bwd,
-                 lambda: ext.dot_interact_bwd(gout, feats)),
+                ("fwd  old [B,F,D]      ", gb_fwd, lambda: fwd_s(feats, out_w)),
+                ("bwd  old [B,F,D]      ", gb_bwd, lambda: bwd_s(gout, feats)),
             ] + runs
         print(f"ext: {args.ext or 'in-tree'}")
     for name, gbytes, fn in runs:
