@@ -1603,6 +1603,99 @@ std::vector<int64_t> wgrad_gemv_plan_py(int64_t K, int64_t N) {
   return {plan.use ? 1 : 0, plan.num_chunks};
 }
 
+// The fp32 forms of the four ops above (mlp_ops.hip, wgrad_splitk_f32.hip):
+// fp32 operands and fp32 results, the same checks, allocator and stream, so
+// they capture into a hipGraph as well.
+std::vector<torch::Tensor> relu_bwd_bias_grad_f32(torch::Tensor grad_out,
+                                                  torch::Tensor y) {
+  CHECK_CUDA(grad_out); CHECK_CUDA(y);
+  CHECK_CONTIG(grad_out); CHECK_CONTIG(y);
+  TORCH_CHECK(grad_out.dtype() == torch::kFloat32 &&
+              y.dtype() == torch::kFloat32, "fp32 required");
+  TORCH_CHECK(grad_out.dim() == 2 && grad_out.sizes() == y.sizes(),
+              "grad_out and y must be [B, N]");
+  TORCH_CHECK(grad_out.device() == y.device(), "operands must share a device");
+  const int64_t B = grad_out.size(0);
+  const int64_t N = grad_out.size(1);
+  TORCH_CHECK(N % 4 == 0 && N < (int64_t(1) << 31), "N % 4 == 0 required");
+  CHECK_ALIGN16(grad_out); CHECK_ALIGN16(y);
+  auto grad_in = torch::empty_like(grad_out);
+  if (B == 0 || N == 0) {
+    return {grad_in, torch::zeros({N}, grad_out.options())};
+  }
+  auto bias_grad = torch::empty({N}, grad_out.options());
+  int64_t rows_per_chunk = 0, num_chunks = 0;
+  relu_bwd_bias_grad_plan(B, (int)N, &rows_per_chunk, &num_chunks);
+  auto slab = torch::empty({num_chunks, N}, grad_out.options());
+  launch_relu_bwd_bias_grad_f32(grad_out.data_ptr(), y.data_ptr(),
+                                grad_in.data_ptr(), slab.data_ptr<float>(),
+                                bias_grad.data_ptr(), B, (int)N,
+                                rows_per_chunk, num_chunks, current_stream());
+  return {grad_in, bias_grad};
+}
+
+torch::Tensor wgrad_splitk_f32(torch::Tensor g, torch::Tensor x,
+                               int64_t splitk, int64_t tile) {
+  CHECK_CUDA(g); CHECK_CUDA(x);
+  CHECK_CONTIG(g); CHECK_CONTIG(x);
+  TORCH_CHECK(g.dtype() == torch::kFloat32 && x.dtype() == torch::kFloat32,
+              "fp32 required");
+  TORCH_CHECK(g.dim() == 2 && x.dim() == 2 && g.size(0) == x.size(0),
+              "g must be [K, M] and x [K, N]");
+  TORCH_CHECK(g.device() == x.device(), "operands must share a device");
+  const int64_t K = g.size(0), M = g.size(1), N = x.size(1);
+  TORCH_CHECK(splitk >= 0, "splitk must not be negative");
+  TORCH_CHECK(tile >= -1 && tile <= 2, "tile must be -1 (plan), 0, 1 or 2");
+  WgradSplitkPlan plan;
+  TORCH_CHECK(wgrad_splitk_f32_plan_with(K, M, N, splitk, (int)tile, &plan),
+              "wgrad_splitk_f32 takes K >= 1, M % 4 == 0 and N % 4 == 0 or "
+              "N <= 16 (tile 2 for N <= 16 only); got K=", K, " M=", M,
+              " N=", N, " tile=", tile);
+  CHECK_ALIGN16(g); CHECK_ALIGN16(x);
+  auto gw = torch::empty({M, N}, g.options());
+  auto slab = torch::empty({plan.splitk, M, plan.np}, g.options());
+  launch_wgrad_splitk_f32(g.data_ptr(), x.data_ptr(), slab.data_ptr<float>(),
+                          gw.data_ptr(), K, (int)M, (int)N, plan,
+                          current_stream());
+  return gw;
+}
+
+std::vector<int64_t> wgrad_splitk_f32_plan_py(int64_t K, int64_t M,
+                                              int64_t N) {
+  WgradSplitkPlan plan;
+  if (!wgrad_splitk_f32_plan(K, M, N, &plan)) return {0, 0, -1};
+  return {plan.use ? 1 : 0, plan.splitk, plan.cfg};
+}
+
+std::vector<torch::Tensor> wgrad_gemv_f32(torch::Tensor g, torch::Tensor x) {
+  CHECK_CUDA(g); CHECK_CUDA(x);
+  CHECK_CONTIG(g); CHECK_CONTIG(x);
+  TORCH_CHECK(g.dtype() == torch::kFloat32 && x.dtype() == torch::kFloat32,
+              "fp32 required");
+  TORCH_CHECK(g.dim() == 2 && x.dim() == 2 && g.size(1) == 1 &&
+              g.size(0) == x.size(0), "g must be [K, 1] and x [K, N]");
+  TORCH_CHECK(g.device() == x.device(), "operands must share a device");
+  const int64_t K = g.size(0), N = x.size(1);
+  WgradGemvPlan plan;
+  TORCH_CHECK(wgrad_gemv_f32_plan(K, N, &plan),
+              "wgrad_gemv_f32 takes K >= 1 and N % 4 == 0; got K=", K,
+              " N=", N);
+  CHECK_ALIGN16(x);
+  auto gw = torch::empty({1, N}, g.options());
+  auto gb = torch::empty({1}, g.options());
+  auto slab = torch::empty({plan.num_chunks, N + 1}, g.options());
+  launch_wgrad_gemv_f32(g.data_ptr(), x.data_ptr(), slab.data_ptr<float>(),
+                        gw.data_ptr(), gb.data_ptr(), K, (int)N, plan,
+                        current_stream());
+  return {gw, gb};
+}
+
+std::vector<int64_t> wgrad_gemv_f32_plan_py(int64_t K, int64_t N) {
+  WgradGemvPlan plan;
+  if (!wgrad_gemv_f32_plan(K, N, &plan)) return {0, 0};
+  return {plan.use ? 1 : 0, plan.num_chunks};
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -1795,4 +1888,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("g"), pybind11::arg("x"));
   m.def("wgrad_gemv_plan", &wgrad_gemv_plan_py,
         "(use, row chunks) for g [K, 1], x [K, N]");
+  m.def("relu_bwd_bias_grad_f32", &relu_bwd_bias_grad_f32,
+        "fp32 ReLU backward + bias gradient in one pass -> (grad_in, "
+        "bias_grad) (gfx950)");
+  m.def("wgrad_splitk_f32", &wgrad_splitk_f32,
+        "fp32 Linear weight gradient g^T x, split-K (MFMA f32, gfx950)",
+        pybind11::arg("g"), pybind11::arg("x"), pybind11::arg("splitk") = 0,
+        pybind11::arg("tile") = -1);
+  m.def("wgrad_splitk_f32_plan", &wgrad_splitk_f32_plan_py,
+        "(use, splitk, tile geometry) for fp32 g [K, M], x [K, N]");
+  m.def("wgrad_gemv_f32", &wgrad_gemv_f32,
+        "fp32 Linear(N, 1) weight and bias gradient -> (gw [1, N], gb [1]) "
+        "(gfx950)",
+        pybind11::arg("g"), pybind11::arg("x"));
+  m.def("wgrad_gemv_f32_plan", &wgrad_gemv_f32_plan_py,
+        "(use, row chunks) for fp32 g [K, 1], x [K, N]");
 }

@@ -6,6 +6,9 @@
 //   row chunk in a fixed order and writes one fp32 row of a slab [R, N] with
 //   plain stores; a second tiny kernel sums the R rows in a fixed order.
 //
+// relu_bwd_bias_grad_f32: the same on fp32 tensors, fp32 bias_grad; a lane
+//   owns 4 columns instead of 8, everything else as above.
+//
 // cross_bwd: the elementwise backward of a low-rank cross layer (DCN-v2),
 //   gu = G * x0, its column sum (the bias gradient) and acc (+)= G * u from
 //   one pass, on the same tiling, slab and finish kernel.
@@ -17,6 +20,7 @@
 namespace {
 
 typedef __attribute__((ext_vector_type(8))) unsigned short u16x8;
+typedef __attribute__((ext_vector_type(4))) float f32x4;
 
 __device__ __forceinline__ float bf16_bits_to_f32(unsigned short h) {
   return __uint_as_float((unsigned int)h << 16);
@@ -93,6 +97,70 @@ __global__ __launch_bounds__(COL_LANES* ROW_LANES) void relu_bwd_bias_partial(
   __syncthreads();
   if (threadIdx.x < TILE_N) {
     const int c = blockIdx.x * TILE_N + threadIdx.x;
+    if (c < N) {
+      float s = 0.f;
+#pragma unroll
+      for (int i = 0; i < ROW_LANES; ++i) s += part[i][threadIdx.x];
+      slab[(int64_t)blockIdx.y * N + c] = s;
+    }
+  }
+}
+
+// relu_bwd_bias_grad_f32, pass 1: fp32 in and out.  The block shape, the row
+// chunking and the LDS fold of relu_bwd_bias_partial; a lane owns 4 adjacent
+// fp32 columns (one 16-byte load of grad_out and of y, one 16-byte store per
+// row), so a block covers TILE_N_F32 = 64 columns.
+constexpr int TILE_N_F32 = COL_LANES * 4;
+
+__global__ __launch_bounds__(COL_LANES* ROW_LANES) void relu_bwd_bias_partial_f32(
+    const float* __restrict__ gout, const float* __restrict__ y,
+    float* __restrict__ gin, float* __restrict__ slab, int64_t B, int N,
+    int64_t rows_per_chunk) {
+  __shared__ float part[ROW_LANES][TILE_N_F32 + 4];
+  const int cl = threadIdx.x % COL_LANES;
+  const int rl = threadIdx.x / COL_LANES;
+  const int col = blockIdx.x * TILE_N_F32 + cl * 4;  // N % 4 == 0: all 4 or none
+  const int64_t r0 = (int64_t)blockIdx.y * rows_per_chunk;
+  int64_t r1 = r0 + rows_per_chunk;
+  if (r1 > B) r1 = B;
+
+  float acc[4] = {0.f, 0.f, 0.f, 0.f};
+
+  if (col < N) {
+    for (int64_t r = r0 + rl; r < r1; r += ROW_LANES * ROW_UNROLL) {
+      f32x4 g[ROW_UNROLL], a[ROW_UNROLL];
+#pragma unroll
+      for (int u = 0; u < ROW_UNROLL; ++u) {
+        const int64_t ru = r + u * ROW_LANES;
+        if (ru < r1) {
+          const int64_t off = ru * N + col;
+          g[u] = *reinterpret_cast<const f32x4*>(gout + off);
+          a[u] = *reinterpret_cast<const f32x4*>(y + off);
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < ROW_UNROLL; ++u) {
+        const int64_t ru = r + u * ROW_LANES;
+        if (ru < r1) {
+          f32x4 o;
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            // NaN in y compares false: the gradient passes, as in torch; a
+            // NaN gradient is passed or zeroed like any other value
+            o[j] = a[u][j] <= 0.f ? 0.f : g[u][j];
+            acc[j] += o[j];
+          }
+          *reinterpret_cast<f32x4*>(gin + ru * N + col) = o;
+        }
+      }
+    }
+  }
+
+#pragma unroll
+  for (int j = 0; j < 4; ++j) part[rl][cl * 4 + j] = acc[j];
+  __syncthreads();
+  if (threadIdx.x < TILE_N_F32) {
+    const int c = blockIdx.x * TILE_N_F32 + threadIdx.x;
     if (c < N) {
       float s = 0.f;
 #pragma unroll
@@ -182,14 +250,21 @@ __global__ __launch_bounds__(COL_LANES* ROW_LANES) void cross_bwd_partial(
   }
 }
 
-// pass 2: bias_grad[n] = bf16(sum_r slab[r][n]), fixed order.
+// pass 2: bias_grad[n] = bf16(sum_r slab[r][n]), fixed order (OUT = float:
+// the fp32 sum as it is).
 // Block = 32 columns x 32 row groups; group g sums rows g, g+32, ...
 constexpr int FIN_COLS = 32;
 constexpr int FIN_GROUPS = 32;
 
+__device__ __forceinline__ void store_sum(unsigned short* dst, float t) {
+  *dst = f32_to_bf16_rne(t);
+}
+__device__ __forceinline__ void store_sum(float* dst, float t) { *dst = t; }
+
+template <typename OUT>
 __global__ __launch_bounds__(FIN_COLS* FIN_GROUPS) void bias_grad_finish(
-    const float* __restrict__ slab, unsigned short* __restrict__ bias_grad,
-    int R, int N) {
+    const float* __restrict__ slab, OUT* __restrict__ bias_grad, int R,
+    int N) {
   __shared__ float part[FIN_GROUPS][FIN_COLS + 1];
   const int c = threadIdx.x % FIN_COLS;
   const int g = threadIdx.x / FIN_COLS;
@@ -205,7 +280,7 @@ __global__ __launch_bounds__(FIN_COLS* FIN_GROUPS) void bias_grad_finish(
     float t = 0.f;
 #pragma unroll
     for (int i = 0; i < FIN_GROUPS; ++i) t += part[i][c];
-    bias_grad[col] = f32_to_bf16_rne(t);
+    store_sum(&bias_grad[col], t);
   }
 }
 
@@ -235,7 +310,7 @@ void launch_relu_bwd_bias_grad(const void* grad_out, const void* y,
                      (const unsigned short*)grad_out,
                      (const unsigned short*)y, (unsigned short*)grad_in, slab,
                      B, N, rows_per_chunk);
-  hipLaunchKernelGGL(bias_grad_finish, dim3((N + FIN_COLS - 1) / FIN_COLS),
+  hipLaunchKernelGGL(bias_grad_finish<unsigned short>, dim3((N + FIN_COLS - 1) / FIN_COLS),
                      dim3(FIN_COLS * FIN_GROUPS), 0, stream,
                      (const float*)slab, (unsigned short*)bias_grad,
                      (int)num_chunks, N);
@@ -253,8 +328,24 @@ void launch_cross_bwd(const void* gout, const void* x0, const void* u,
                      (const unsigned short*)gout, (const unsigned short*)x0,
                      (const unsigned short*)u, (unsigned short*)acc,
                      (unsigned short*)gu, slab, B, N, rows_per_chunk);
-  hipLaunchKernelGGL(bias_grad_finish, dim3((N + FIN_COLS - 1) / FIN_COLS),
+  hipLaunchKernelGGL(bias_grad_finish<unsigned short>, dim3((N + FIN_COLS - 1) / FIN_COLS),
                      dim3(FIN_COLS * FIN_GROUPS), 0, stream,
                      (const float*)slab, (unsigned short*)bias_grad,
                      (int)num_chunks, N);
+}
+
+void launch_relu_bwd_bias_grad_f32(const void* grad_out, const void* y,
+                                   void* grad_in, float* slab, void* bias_grad,
+                                   int64_t B, int N, int64_t rows_per_chunk,
+                                   int64_t num_chunks, hipStream_t stream) {
+  const int col_tiles = (N + TILE_N_F32 - 1) / TILE_N_F32;
+  dim3 grid(col_tiles, (unsigned)num_chunks);
+  hipLaunchKernelGGL(relu_bwd_bias_partial_f32, grid,
+                     dim3(COL_LANES * ROW_LANES), 0, stream,
+                     (const float*)grad_out, (const float*)y, (float*)grad_in,
+                     slab, B, N, rows_per_chunk);
+  hipLaunchKernelGGL(bias_grad_finish<float>, dim3((N + FIN_COLS - 1) / FIN_COLS),
+                     dim3(FIN_COLS * FIN_GROUPS), 0, stream,
+                     (const float*)slab, (float*)bias_grad, (int)num_chunks,
+                     N);
 }

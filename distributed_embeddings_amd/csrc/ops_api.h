@@ -283,6 +283,13 @@ void launch_relu_bwd_bias_grad(const void* grad_out, const void* y,
                                int64_t B, int N, int64_t rows_per_chunk,
                                int64_t num_chunks, hipStream_t stream);
 
+// The same on fp32 tensors with an fp32 bias_grad, N % 4 == 0, 16-byte
+// aligned; the plan and the slab shape are those above.
+void launch_relu_bwd_bias_grad_f32(const void* grad_out, const void* y,
+                                   void* grad_in, float* slab, void* bias_grad,
+                                   int64_t B, int N, int64_t rows_per_chunk,
+                                   int64_t num_chunks, hipStream_t stream);
+
 // mlp_ops.hip.  cross_bwd, the elementwise backward of one low-rank cross
 // layer x_{l+1} = x0 * u + x_l, all bf16 [B, N] with N % 8 == 0 and 16-byte
 // aligned: gu = bf16(gout * x0), bias_grad = bf16(column sums of gu) and, in
@@ -342,6 +349,24 @@ bool wgrad_gemv_plan(int64_t K, int64_t N, WgradGemvPlan* plan);
 void launch_wgrad_gemv(const void* g, const void* x, float* slab, void* gw,
                        void* gb, int64_t K, int N, const WgradGemvPlan& plan,
                        hipStream_t stream);
+
+// wgrad_splitk_f32.hip.  The two above on fp32 operands with fp32 results:
+// gw [M, N] = g^T x for g [K, M], x [K, N], M % 4 == 0 and N % 4 == 0 or
+// N <= 16 (slab [splitk, M, np], splitk capped at ceil(K / 32)), and
+// gw [N], gb [1] for g [K], x [K, N], N % 4 == 0 (slab [num_chunks, N + 1]).
+// The plans have the bf16 plans' fields and choices of their own.
+bool wgrad_splitk_f32_plan(int64_t K, int64_t M, int64_t N,
+                           WgradSplitkPlan* plan);
+bool wgrad_splitk_f32_plan_with(int64_t K, int64_t M, int64_t N,
+                                int64_t splitk, int tile,
+                                WgradSplitkPlan* plan);
+void launch_wgrad_splitk_f32(const void* g, const void* x, float* slab,
+                             void* gw, int64_t K, int M, int N,
+                             const WgradSplitkPlan& plan, hipStream_t stream);
+bool wgrad_gemv_f32_plan(int64_t K, int64_t N, WgradGemvPlan* plan);
+void launch_wgrad_gemv_f32(const void* g, const void* x, float* slab, void* gw,
+                           void* gb, int64_t K, int N,
+                           const WgradGemvPlan& plan, hipStream_t stream);
 
 size_t custom_radix_sort_hist_elems(int64_t n);
 int custom_radix_sort_num_variants();

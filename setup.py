@@ -24,6 +24,7 @@ ext = CUDAExtension(
         "distributed_embeddings_amd/csrc/mlp_ops.hip",
         "distributed_embeddings_amd/csrc/cross_ops.hip",
         "distributed_embeddings_amd/csrc/wgrad_splitk.hip",
+        "distributed_embeddings_amd/csrc/wgrad_splitk_f32.hip",
         "distributed_embeddings_amd/csrc/pack_ids.hip",
     ],
     extra_compile_args={
