@@ -1528,6 +1528,118 @@ std::vector<torch::Tensor> cross_concat_bwd(torch::Tensor gx0,
   return {gbottom, gpacked};
 }
 
+// Concat + average pool (csrc/concat_pool.hip).  The kernels take bf16 and
+// fp32 only, on both sides.
+static bool concat_pool_is_bf16(const torch::Tensor& t, const char* what) {
+  TORCH_CHECK(t.dtype() == torch::kBFloat16 || t.dtype() == torch::kFloat32,
+              "concat_pool: ", what, " must be bf16 or fp32");
+  return t.dtype() == torch::kBFloat16;
+}
+
+static void check_concat_pool_shape(int64_t B, int64_t W, int64_t Nn,
+                                    int64_t stride) {
+  TORCH_CHECK(stride >= 1 && stride <= kConcatPoolMaxStride,
+              "concat_pool: stride must be in [1, ", kConcatPoolMaxStride, "]");
+  // columns and the rows of one tile are indexed in 32 bits
+  TORCH_CHECK(W >= 1 && W + Nn < (int64_t(1) << 25),
+              "concat_pool: row too wide");
+  TORCH_CHECK(B >= 0, "negative batch");
+}
+
+// out [B, ceil(W / stride) + Nn] from inputs[t] [B, w_t] and numerical
+// [B, Nn]: no sync, one allocation, launches on the current stream.
+torch::Tensor concat_pool_fwd(std::vector<torch::Tensor> inputs,
+                              std::optional<torch::Tensor> numerical,
+                              int64_t stride, bool out_bf16) {
+  TORCH_CHECK(!inputs.empty(), "concat_pool: needs at least one input");
+  const auto& first = inputs[0];
+  CHECK_CUDA(first);
+  TORCH_CHECK(first.dim() == 2, "concat_pool: inputs must be [B, w]");
+  const bool in_bf16 = concat_pool_is_bf16(first, "inputs");
+  const int64_t ch = in_bf16 ? 8 : 4;
+  const int64_t B = first.size(0);
+  std::vector<ConcatPoolInput> descs(inputs.size());
+  int64_t W = 0;
+  for (size_t t = 0; t < inputs.size(); ++t) {
+    const auto& x = inputs[t];
+    TORCH_CHECK(x.is_cuda() && x.device() == first.device() &&
+                x.dtype() == first.dtype() && x.dim() == 2 && x.size(0) == B,
+                "concat_pool: input ", t, " must match input 0 in device, "
+                "dtype and batch");
+    TORCH_CHECK(x.is_contiguous(), "concat_pool: input ", t,
+                " must be contiguous");
+    TORCH_CHECK(x.size(1) >= ch && x.size(1) % ch == 0, "concat_pool: input ",
+                t, " must have a width that is a multiple of ", ch);
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0,
+                "concat_pool: input ", t, " must be 16-byte aligned");
+    TORCH_CHECK(W + x.size(1) < (int64_t(1) << 25), "concat_pool: row too wide");
+    descs[t] = {x.data_ptr(), (int32_t)W, (int32_t)x.size(1)};
+    W += x.size(1);
+  }
+  int64_t Nn = 0;
+  bool num_bf16 = false;
+  const void* num_ptr = nullptr;
+  if (numerical.has_value()) {
+    const auto& num = *numerical;
+    CHECK_CUDA(num); CHECK_CONTIG(num);
+    TORCH_CHECK(num.dim() == 2 && num.size(0) == B &&
+                num.device() == first.device(),
+                "concat_pool: numerical must be [B, Nn] on the inputs' device");
+    num_bf16 = concat_pool_is_bf16(num, "numerical");
+    Nn = num.size(1);
+    num_ptr = num.data_ptr();
+  }
+  check_concat_pool_shape(B, W, Nn, stride);
+  const int64_t Wp = (W + stride - 1) / stride;
+  auto out = torch::empty(
+      {B, Wp + Nn},
+      first.options().dtype(out_bf16 ? torch::kBFloat16 : torch::kFloat32));
+  launch_concat_pool_fwd(descs.data(), (int)descs.size(), in_bf16, num_ptr,
+                         num_bf16, (int)Nn, out.data_ptr(), out_bf16, B,
+                         (int)W, (int)stride, current_stream());
+  return out;
+}
+
+// The inputs' gradients from gout [B, ceil(W / stride) + Nn]: contiguous
+// [B, widths[t]] views, in input order, of one flat allocation.
+std::vector<torch::Tensor> concat_pool_bwd(torch::Tensor gout,
+                                           std::vector<int64_t> widths,
+                                           int64_t stride, int64_t Nn,
+                                           bool in_bf16) {
+  CHECK_CUDA(gout); CHECK_CONTIG(gout);
+  TORCH_CHECK(gout.dim() == 2 && !widths.empty() && Nn >= 0,
+              "concat_pool: gout must be [B, Wp + Nn]");
+  const bool gout_bf16 = concat_pool_is_bf16(gout, "gout");
+  const int64_t ch = in_bf16 ? 8 : 4;
+  const int64_t B = gout.size(0);
+  int64_t W = 0;
+  for (int64_t w : widths) {
+    TORCH_CHECK(w >= ch && w % ch == 0,
+                "concat_pool: widths must be multiples of ", ch);
+    W += w;
+    TORCH_CHECK(W < (int64_t(1) << 25), "concat_pool: row too wide");
+  }
+  check_concat_pool_shape(B, W, Nn, stride);
+  TORCH_CHECK(gout.size(1) == (W + stride - 1) / stride + Nn,
+              "concat_pool: gout has the wrong width");
+  auto flat = torch::empty(
+      {B * W},
+      gout.options().dtype(in_bf16 ? torch::kBFloat16 : torch::kFloat32));
+  std::vector<torch::Tensor> gins(widths.size());
+  std::vector<ConcatPoolInput> descs(widths.size());
+  int64_t begin = 0;
+  for (size_t t = 0; t < widths.size(); ++t) {
+    // B * begin elements: a multiple of 16 bytes, as begin is one of ch
+    gins[t] = flat.narrow(0, B * begin, B * widths[t]).view({B, widths[t]});
+    descs[t] = {gins[t].data_ptr(), (int32_t)begin, (int32_t)widths[t]};
+    begin += widths[t];
+  }
+  launch_concat_pool_bwd(gout.data_ptr(), gout_bf16, descs.data(),
+                         (int)descs.size(), in_bf16, (int)Nn, B, (int)W,
+                         (int)stride, current_stream());
+  return gins;
+}
+
 // Weight gradient of a Linear layer, gw = bf16(g^T x) with fp32 accumulation
 // (wgrad_splitk.hip).  The slab comes from the torch allocator and both
 // launches go on the current stream: capturable.  splitk > 0 and tile >= 0
@@ -1877,6 +1989,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "gradient of x0 -> (gbottom, gpacked) (gfx950)",
         pybind11::arg("gx0"), pybind11::arg("perm"),
         pybind11::arg("sample_major"));
+  m.def("concat_pool_fwd", &concat_pool_fwd,
+        "[average pool of the concatenated inputs | numerical] (gfx950)",
+        pybind11::arg("inputs"), pybind11::arg("numerical"),
+        pybind11::arg("stride"), pybind11::arg("out_bf16"));
+  m.def("concat_pool_bwd", &concat_pool_bwd,
+        "gradient of concat_pool_fwd's output -> the inputs' gradients "
+        "(gfx950)",
+        pybind11::arg("gout"), pybind11::arg("widths"),
+        pybind11::arg("stride"), pybind11::arg("num_numerical"),
+        pybind11::arg("in_bf16"));
   m.def("wgrad_splitk", &wgrad_splitk,
         "Linear weight gradient bf16(g^T x), split-K (MFMA bf16, gfx950)",
         pybind11::arg("g"), pybind11::arg("x"), pybind11::arg("splitk") = 0,

@@ -315,6 +315,34 @@ void launch_cross_concat_bwd(const void* gx0, const int* perm, void* gbottom,
                              void* gpacked, int64_t B, int P, int D,
                              int64_t sb, int64_t sp, hipStream_t stream);
 
+// concat_pool.hip.  out [B, Wp + Nn] = [average pool of the inputs side by
+// side | numerical], window = stride = S, Wp = ceil(W / S), the last window
+// divided by its real length.  Input t is contiguous [B, width], 16-byte
+// aligned, at concatenated columns [begin, begin + width); the begins ascend
+// without gaps from 0 to W and every width is a positive multiple of 8 (bf16)
+// or 4 (fp32).  numerical is contiguous [B, Nn] bf16 or fp32, or null with
+// Nn == 0.  1 <= S <= kConcatPoolMaxStride.  std::invalid_argument outside
+// that.  The descriptors go by value in the kernel arguments,
+// kConcatPoolMaxInputs per launch; more inputs take several launches over
+// consecutive ranges of output columns.
+constexpr int kConcatPoolMaxInputs = 224;  // 16 bytes each, < 4 KB
+constexpr int kConcatPoolMaxStride = 256;
+struct ConcatPoolInput {
+  void* ptr;
+  int32_t begin;
+  int32_t width;
+};
+void launch_concat_pool_fwd(const ConcatPoolInput* in, int nin, bool in_bf16,
+                            const void* numerical, bool num_bf16, int Nn,
+                            void* out, bool out_bf16, int64_t B, int W, int S,
+                            hipStream_t stream);
+// gin[t].ptr receives gout[b, (begin + j) / S] / (window length) in the
+// inputs' type; every element is written once.  gout is [B, Wp + Nn].
+void launch_concat_pool_bwd(const void* gout, bool gout_bf16,
+                            const ConcatPoolInput* gin, int nin, bool in_bf16,
+                            int Nn, int64_t B, int W, int S,
+                            hipStream_t stream);
+
 // wgrad_splitk.hip.  gw [M, N] = bf16(g^T x) for bf16 g [K, M], x [K, N], fp32
 // accumulation, one rounding: split-K partial products into the fp32 slab
 // [splitk, M, np], then a fixed-order sum.  M % 8 == 0; N % 8 == 0 or N <= 16.

@@ -14,6 +14,7 @@ import torch
 from torch import nn
 
 from ..layers.embedding import Embedding
+from ..ops.concat_pool import concat_avg_pool, fused_ok
 from ..ops.mlp import MLP
 from ..parallel import comm
 from ..parallel.dist_embedding import DistributedEmbedding
@@ -90,6 +91,15 @@ class SyntheticModel(nn.Module):
         # under autocast the MLP runs bf16: ask for bf16 embedding outputs
         want = torch.bfloat16 if torch.is_autocast_enabled() else numerical.dtype
         embs = self.embeddings(list(cat_features), output_dtype=want)
+        # cat + pool + cat as one HIP pass when the embedding outputs can be
+        # read where they are (ops/concat_pool.py); bf16 out under autocast,
+        # the bits the MLP's own cast of the promoted fp32 row gives
+        if (self.interact is not None and numerical.is_cuda
+                and all(e.dtype == want for e in embs)
+                and fused_ok(embs, numerical, self.interact_stride, want)):
+            return self.mlp(concat_avg_pool(embs, numerical,
+                                            self.interact_stride,
+                                            out_dtype=want))
         x = torch.cat([e.to(want) for e in embs], dim=1)
         if self.interact is not None:
             x = self.interact(x.unsqueeze(1)).squeeze(1)

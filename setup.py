@@ -26,6 +26,7 @@ ext = CUDAExtension(
         "distributed_embeddings_amd/csrc/wgrad_splitk.hip",
         "distributed_embeddings_amd/csrc/wgrad_splitk_f32.hip",
         "distributed_embeddings_amd/csrc/pack_ids.hip",
+        "distributed_embeddings_amd/csrc/concat_pool.hip",
     ],
     extra_compile_args={
         "cxx": ["-O3", "-std=c++17"],
