@@ -1422,15 +1422,18 @@ std::vector<torch::Tensor> relu_bwd_bias_grad(torch::Tensor grad_out,
 // acc = (init ? 0 : acc) + G * u, from one pass.  Returns (gu, gb).  Outputs
 // and the fp32 partial slab come from the torch allocator and both launches
 // go on the current stream, so the op can be captured in a hipGraph.
-std::vector<torch::Tensor> cross_bwd(torch::Tensor G, torch::Tensor x0,
-                                     torch::Tensor u, torch::Tensor acc,
-                                     bool init) {
+// f32: fp32 tensors with N % 4 == 0 (cross_bwd_f32), else bf16 with N % 8.
+static std::vector<torch::Tensor> cross_bwd_impl(torch::Tensor G,
+                                                 torch::Tensor x0,
+                                                 torch::Tensor u,
+                                                 torch::Tensor acc, bool init,
+                                                 bool f32) {
   CHECK_CUDA(G); CHECK_CUDA(x0); CHECK_CUDA(u); CHECK_CUDA(acc);
   CHECK_CONTIG(G); CHECK_CONTIG(x0); CHECK_CONTIG(u); CHECK_CONTIG(acc);
-  TORCH_CHECK(G.dtype() == torch::kBFloat16 &&
-              x0.dtype() == torch::kBFloat16 &&
-              u.dtype() == torch::kBFloat16 &&
-              acc.dtype() == torch::kBFloat16, "bf16 required");
+  const auto dtype = f32 ? torch::kFloat32 : torch::kBFloat16;
+  TORCH_CHECK(G.dtype() == dtype && x0.dtype() == dtype &&
+              u.dtype() == dtype && acc.dtype() == dtype,
+              f32 ? "fp32 required" : "bf16 required");
   TORCH_CHECK(G.dim() == 2 && G.sizes() == x0.sizes() &&
               G.sizes() == u.sizes() && G.sizes() == acc.sizes(),
               "G, x0, u and acc must be [B, N]");
@@ -1438,7 +1441,8 @@ std::vector<torch::Tensor> cross_bwd(torch::Tensor G, torch::Tensor x0,
               G.device() == acc.device(), "operands must share a device");
   const int64_t B = G.size(0);
   const int64_t N = G.size(1);
-  TORCH_CHECK(N % 8 == 0 && N < (int64_t(1) << 31), "N % 8 == 0 required");
+  TORCH_CHECK(N % (f32 ? 4 : 8) == 0 && N < (int64_t(1) << 31),
+              f32 ? "N % 4 == 0 required" : "N % 8 == 0 required");
   CHECK_ALIGN16(G); CHECK_ALIGN16(x0); CHECK_ALIGN16(u); CHECK_ALIGN16(acc);
   auto gu = torch::empty_like(G);
   if (B == 0 || N == 0) {
@@ -1453,28 +1457,47 @@ std::vector<torch::Tensor> cross_bwd(torch::Tensor G, torch::Tensor x0,
   relu_bwd_bias_grad_plan(B, (int)N, &rows_per_chunk, &num_chunks);
   auto slab = torch::empty({num_chunks, N},
                            G.options().dtype(torch::kFloat32));
-  launch_cross_bwd(G.data_ptr(), x0.data_ptr(), u.data_ptr(), acc.data_ptr(),
-                   init, gu.data_ptr(), slab.data_ptr<float>(), gb.data_ptr(),
-                   B, (int)N, rows_per_chunk, num_chunks, current_stream());
+  (f32 ? launch_cross_bwd_f32 : launch_cross_bwd)(
+      G.data_ptr(), x0.data_ptr(), u.data_ptr(), acc.data_ptr(), init,
+      gu.data_ptr(), slab.data_ptr<float>(), gb.data_ptr(), B, (int)N,
+      rows_per_chunk, num_chunks, current_stream());
   return {gu, gb};
+}
+
+std::vector<torch::Tensor> cross_bwd(torch::Tensor G, torch::Tensor x0,
+                                     torch::Tensor u, torch::Tensor acc,
+                                     bool init) {
+  return cross_bwd_impl(G, x0, u, acc, init, false);
+}
+
+std::vector<torch::Tensor> cross_bwd_f32(torch::Tensor G, torch::Tensor x0,
+                                         torch::Tensor u, torch::Tensor acc,
+                                         bool init) {
+  return cross_bwd_impl(G, x0, u, acc, init, true);
 }
 
 // Shapes of the cross interaction's input assembly: bottom [B, D], packed
 // [P, B, D] (feature-major) or [B, P, D] (sample-major), x0 [B, (P+1)*D].
-static void check_cross_concat_shape(int64_t B, int64_t P, int64_t D) {
-  TORCH_CHECK(P >= 1 && D >= 8 && D % 8 == 0,
-              "P >= 1 and D % 8 == 0 required (got P=", P, ", D=", D, ")");
-  // a block walks 16 rows of x0 with 32-bit indices
-  TORCH_CHECK((P + 1) * D < (int64_t(1) << 27), "row of x0 too wide");
+// vec is the elements of a 16-byte chunk: 8 for bf16, 4 for fp32.
+static void check_cross_concat_shape(int64_t B, int64_t P, int64_t D,
+                                     int64_t vec) {
+  TORCH_CHECK(P >= 1 && D >= vec && D % vec == 0,
+              "P >= 1 and D % ", vec, " == 0 required (got P=", P, ", D=", D,
+              ")");
+  // a block walks 16 rows of x0 with 32-bit indices: 2^27 bf16, 2^26 fp32
+  TORCH_CHECK((P + 1) * D < (int64_t(1) << 24) * vec, "row of x0 too wide");
   TORCH_CHECK(B >= 0, "negative batch");
 }
 
-torch::Tensor cross_concat_fwd(torch::Tensor bottom, torch::Tensor packed,
-                               torch::Tensor perm, bool sample_major) {
+static torch::Tensor cross_concat_fwd_impl(torch::Tensor bottom,
+                                           torch::Tensor packed,
+                                           torch::Tensor perm,
+                                           bool sample_major, bool f32) {
   CHECK_CUDA(bottom); CHECK_CUDA(packed); CHECK_CUDA(perm);
   CHECK_CONTIG(bottom); CHECK_CONTIG(packed); CHECK_CONTIG(perm);
-  TORCH_CHECK(bottom.dtype() == torch::kBFloat16 &&
-              packed.dtype() == torch::kBFloat16, "bf16 required");
+  const auto dtype = f32 ? torch::kFloat32 : torch::kBFloat16;
+  TORCH_CHECK(bottom.dtype() == dtype && packed.dtype() == dtype,
+              f32 ? "fp32 required" : "bf16 required");
   TORCH_CHECK(perm.dtype() == torch::kInt32, "perm must be int32");
   TORCH_CHECK(bottom.dim() == 2 && packed.dim() == 3,
               "bottom [B,D], packed 3-D");
@@ -1487,25 +1510,37 @@ torch::Tensor cross_concat_fwd(torch::Tensor bottom, torch::Tensor packed,
   TORCH_CHECK(packed.size(sample_major ? 0 : 1) == B && packed.size(2) == D,
               "shape mismatch");
   TORCH_CHECK(perm.numel() == P, "perm must have P entries");
-  check_cross_concat_shape(B, P, D);
+  check_cross_concat_shape(B, P, D, f32 ? 4 : 8);
   CHECK_ALIGN16(bottom); CHECK_ALIGN16(packed);
   const int64_t sb = sample_major ? P : 1;
   const int64_t sp = sample_major ? 1 : B;
   auto x0 = torch::empty({B, (P + 1) * D}, bottom.options());
-  launch_cross_concat_fwd(bottom.data_ptr(), packed.data_ptr(),
-                          perm.data_ptr<int>(), x0.data_ptr(), B, (int)P,
-                          (int)D, sb, sp, current_stream());
+  (f32 ? launch_cross_concat_f32_fwd : launch_cross_concat_fwd)(
+      bottom.data_ptr(), packed.data_ptr(), perm.data_ptr<int>(),
+      x0.data_ptr(), B, (int)P, (int)D, sb, sp, current_stream());
   return x0;
+}
+
+torch::Tensor cross_concat_fwd(torch::Tensor bottom, torch::Tensor packed,
+                               torch::Tensor perm, bool sample_major) {
+  return cross_concat_fwd_impl(bottom, packed, perm, sample_major, false);
+}
+
+torch::Tensor cross_concat_f32_fwd(torch::Tensor bottom, torch::Tensor packed,
+                                   torch::Tensor perm, bool sample_major) {
+  return cross_concat_fwd_impl(bottom, packed, perm, sample_major, true);
 }
 
 // (gbottom [B, D], gpacked in packed's layout) from gx0 [B, (P+1)*D]; perm
 // has to be a permutation of [0, P).
-std::vector<torch::Tensor> cross_concat_bwd(torch::Tensor gx0,
-                                            torch::Tensor perm,
-                                            bool sample_major) {
+static std::vector<torch::Tensor> cross_concat_bwd_impl(torch::Tensor gx0,
+                                                        torch::Tensor perm,
+                                                        bool sample_major,
+                                                        bool f32) {
   CHECK_CUDA(gx0); CHECK_CUDA(perm);
   CHECK_CONTIG(gx0); CHECK_CONTIG(perm);
-  TORCH_CHECK(gx0.dtype() == torch::kBFloat16, "bf16 required");
+  TORCH_CHECK(gx0.dtype() == (f32 ? torch::kFloat32 : torch::kBFloat16),
+              f32 ? "fp32 required" : "bf16 required");
   TORCH_CHECK(perm.dtype() == torch::kInt32, "perm must be int32");
   TORCH_CHECK(gx0.dim() == 2 && perm.dim() == 1 && perm.numel() >= 1,
               "gx0 [B, (P+1)*D], perm [P]");
@@ -1515,17 +1550,29 @@ std::vector<torch::Tensor> cross_concat_bwd(torch::Tensor gx0,
   TORCH_CHECK(gx0.size(1) % (P + 1) == 0,
               "gx0 width must be a multiple of P + 1");
   const int64_t D = gx0.size(1) / (P + 1);
-  check_cross_concat_shape(B, P, D);
+  check_cross_concat_shape(B, P, D, f32 ? 4 : 8);
   CHECK_ALIGN16(gx0);
   const int64_t sb = sample_major ? P : 1;
   const int64_t sp = sample_major ? 1 : B;
   auto gbottom = torch::empty({B, D}, gx0.options());
   auto gpacked = sample_major ? torch::empty({B, P, D}, gx0.options())
                               : torch::empty({P, B, D}, gx0.options());
-  launch_cross_concat_bwd(gx0.data_ptr(), perm.data_ptr<int>(),
-                          gbottom.data_ptr(), gpacked.data_ptr(), B, (int)P,
-                          (int)D, sb, sp, current_stream());
+  (f32 ? launch_cross_concat_f32_bwd : launch_cross_concat_bwd)(
+      gx0.data_ptr(), perm.data_ptr<int>(), gbottom.data_ptr(),
+      gpacked.data_ptr(), B, (int)P, (int)D, sb, sp, current_stream());
   return {gbottom, gpacked};
+}
+
+std::vector<torch::Tensor> cross_concat_bwd(torch::Tensor gx0,
+                                            torch::Tensor perm,
+                                            bool sample_major) {
+  return cross_concat_bwd_impl(gx0, perm, sample_major, false);
+}
+
+std::vector<torch::Tensor> cross_concat_f32_bwd(torch::Tensor gx0,
+                                                torch::Tensor perm,
+                                                bool sample_major) {
+  return cross_concat_bwd_impl(gx0, perm, sample_major, true);
 }
 
 // Concat + average pool (csrc/concat_pool.hip).  The kernels take bf16 and
@@ -1987,6 +2034,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("perm"), pybind11::arg("sample_major"));
   m.def("cross_concat_bwd", &cross_concat_bwd,
         "gradient of x0 -> (gbottom, gpacked) (gfx950)",
+        pybind11::arg("gx0"), pybind11::arg("perm"),
+        pybind11::arg("sample_major"));
+  m.def("cross_bwd_f32", &cross_bwd_f32,
+        "fp32 low-rank cross layer backward: gu = G * x0, its column sum, "
+        "and acc (+)= G * u in place, one pass -> (gu, gb) (gfx950)",
+        pybind11::arg("G"), pybind11::arg("x0"), pybind11::arg("u"),
+        pybind11::arg("acc"), pybind11::arg("init"));
+  m.def("cross_concat_f32_fwd", &cross_concat_f32_fwd,
+        "fp32 x0 = [bottom | packed rows in perm order] (gfx950)",
+        pybind11::arg("bottom"), pybind11::arg("packed"),
+        pybind11::arg("perm"), pybind11::arg("sample_major"));
+  m.def("cross_concat_f32_bwd", &cross_concat_f32_bwd,
+        "fp32 gradient of x0 -> (gbottom, gpacked) (gfx950)",
         pybind11::arg("gx0"), pybind11::arg("perm"),
         pybind11::arg("sample_major"));
   m.def("concat_pool_fwd", &concat_pool_fwd,

@@ -4,7 +4,8 @@
 //   from bottom [B, D] and the packed embeddings, [P, B, D] feature-major or
 //   [B, P, D] sample-major (strides sb, sp as in dot_interact.hip).
 // cross_concat_bwd: the reverse split of x0's gradient.
-// Both are 16-byte copies: a lane moves 8 adjacent bf16 of one feature.
+// Both are 16-byte copies: a lane moves 8 adjacent bf16 of one feature, or 4
+// adjacent fp32 (the launch_cross_concat_f32_* entry points, at the end).
 
 #include <hip/hip_runtime.h>
 
@@ -96,4 +97,24 @@ void launch_cross_concat_bwd(const void* gx0, const int* perm, void* gbottom,
   // the backward instance only reads gx0
   launch_concat<false>(gbottom, gpacked, perm, const_cast<void*>(gx0), B, P,
                        D, sb, sp, stream);
+}
+
+// fp32: the kernels do no arithmetic, and a row of D fp32 with D % 4 == 0 is,
+// byte for byte, a row of 2*D bf16 with 2*D % 8 == 0 at the same sb and sp.
+// So the same two instantiations run on the same bytes: a lane moves 4
+// adjacent fp32 of one feature.
+void launch_cross_concat_f32_fwd(const void* bottom, const void* packed,
+                                 const int* perm, void* x0, int64_t B, int P,
+                                 int D, int64_t sb, int64_t sp,
+                                 hipStream_t stream) {
+  launch_cross_concat_fwd(bottom, packed, perm, x0, B, P, 2 * D, sb, sp,
+                          stream);
+}
+
+void launch_cross_concat_f32_bwd(const void* gx0, const int* perm,
+                                 void* gbottom, void* gpacked, int64_t B,
+                                 int P, int D, int64_t sb, int64_t sp,
+                                 hipStream_t stream) {
+  launch_cross_concat_bwd(gx0, perm, gbottom, gpacked, B, P, 2 * D, sb, sp,
+                          stream);
 }

@@ -12,6 +12,9 @@
 // cross_bwd: the elementwise backward of a low-rank cross layer (DCN-v2),
 //   gu = G * x0, its column sum (the bias gradient) and acc (+)= G * u from
 //   one pass, on the same tiling, slab and finish kernel.
+//
+// cross_bwd_f32: the same on fp32 tensors with an fp32 bias gradient, on the
+//   tiling of relu_bwd_bias_grad_f32.
 
 #include <hip/hip_runtime.h>
 
@@ -250,6 +253,101 @@ __global__ __launch_bounds__(COL_LANES* ROW_LANES) void cross_bwd_partial(
   }
 }
 
+// cross_bwd_f32, pass 1: the same backward on fp32 [B, N], N % 4 == 0.
+//   gu  = G * x0                      (one fp32 multiply: torch's product)
+//   acc = INIT ? G * u : acc + G * u  (in place; mul + add or one fma)
+//   slab[chunk][n] = sum over the chunk's rows of gu
+// The block of relu_bwd_bias_partial_f32: a lane owns 4 adjacent fp32 columns,
+// a block 64 columns, grid = (ceil(N / 64), row chunks).  A 16-byte fp32 load
+// is 4 VGPRs where the bf16 kernel's 8 values unpack from 4 into 8 only at
+// use, so the loads of one row group (G, x0, u, acc) hold 16 VGPRs until
+// their row is done.  CROSS_F32_UNROLL = 2 row groups keep 8 loads, 128 bytes
+// a lane, in flight in 32 VGPRs and leave the kernel under the 64 VGPRs of
+// 8 waves/SIMD; gu and the new acc overwrite x0's and u's registers.  3 or 4
+// groups need 48 or 64 VGPRs of load data alone, which halves the waves per
+// SIMD for the same bytes in flight per SIMD.
+// INIT never reads acc, so acc may hold anything (NaN included) beforehand.
+// acc is read and written by the same lane at the same address only.
+constexpr int CROSS_F32_UNROLL = 2;
+
+template <bool INIT>
+__global__ __launch_bounds__(COL_LANES* ROW_LANES) void cross_bwd_partial_f32(
+    const float* __restrict__ gout, const float* __restrict__ x0,
+    const float* __restrict__ u, float* acc, float* __restrict__ gu,
+    float* __restrict__ slab, int64_t B, int N, int64_t rows_per_chunk) {
+  // rows of 68 floats: every lane's 4 sums are one aligned 16-byte LDS store
+  __shared__ __attribute__((aligned(16))) float part[ROW_LANES][TILE_N_F32 + 4];
+  const int cl = threadIdx.x % COL_LANES;
+  const int rl = threadIdx.x / COL_LANES;
+  const int col = blockIdx.x * TILE_N_F32 + cl * 4;  // N % 4 == 0: all 4 or none
+  const int64_t r0 = (int64_t)blockIdx.y * rows_per_chunk;
+  int64_t r1 = r0 + rows_per_chunk;
+  if (r1 > B) r1 = B;
+
+  f32x4 sum = {0.f, 0.f, 0.f, 0.f};
+
+  if (col < N) {
+    for (int64_t r = r0 + rl; r < r1; r += ROW_LANES * CROSS_F32_UNROLL) {
+      f32x4 g[CROSS_F32_UNROLL], x[CROSS_F32_UNROLL], w[CROSS_F32_UNROLL],
+          a[CROSS_F32_UNROLL];
+#pragma unroll
+      for (int k = 0; k < CROSS_F32_UNROLL; ++k) {
+        const int64_t rk = r + k * ROW_LANES;
+        if (rk < r1) {
+          const int64_t off = rk * N + col;
+          g[k] = *reinterpret_cast<const f32x4*>(gout + off);
+          x[k] = *reinterpret_cast<const f32x4*>(x0 + off);
+          w[k] = *reinterpret_cast<const f32x4*>(u + off);
+          if (!INIT) a[k] = *reinterpret_cast<const f32x4*>(acc + off);
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < CROSS_F32_UNROLL; ++k) {
+        const int64_t rk = r + k * ROW_LANES;
+        if (rk < r1) {
+          f32x4 o;
+          {
+            // the column sum adds the rounded product that gu stores, not an
+            // fma on the exact one
+#pragma clang fp contract(off)
+            o = g[k] * x[k];
+            sum += o;
+          }
+          // INIT: the product alone, as torch rounds it.  Otherwise the
+          // compiler may contract to one fma: one rounding of acc + G*u
+          // instead of two, inside the documented bound either way.
+          const f32x4 s = INIT ? g[k] * w[k] : a[k] + g[k] * w[k];
+          const int64_t off = rk * N + col;
+          *reinterpret_cast<f32x4*>(gu + off) = o;
+          *reinterpret_cast<f32x4*>(acc + off) = s;
+        }
+      }
+    }
+  }
+
+  // every thread gets here: lanes past N and row lanes past the chunk's end
+  // hand zeros to the fold
+  *reinterpret_cast<f32x4*>(&part[rl][cl * 4]) = sum;
+  __syncthreads();
+  if (threadIdx.x < TILE_N_F32) {
+    const int c = blockIdx.x * TILE_N_F32 + threadIdx.x;
+    if (c < N) {
+      // a fixed pairwise tree over the 16 row lanes, i with i + 8, 4, 2, 1:
+      // the 15 adds of a chain in 4 dependent steps, and 4 roundings on any
+      // path to the result instead of up to 15
+      float s[ROW_LANES];
+#pragma unroll
+      for (int i = 0; i < ROW_LANES; ++i) s[i] = part[i][threadIdx.x];
+#pragma unroll
+      for (int w = ROW_LANES / 2; w > 0; w /= 2) {
+#pragma unroll
+        for (int i = 0; i < w; ++i) s[i] += s[i + w];
+      }
+      slab[(int64_t)blockIdx.y * N + c] = s[0];
+    }
+  }
+}
+
 // pass 2: bias_grad[n] = bf16(sum_r slab[r][n]), fixed order (OUT = float:
 // the fp32 sum as it is).
 // Block = 32 columns x 32 row groups; group g sums rows g, g+32, ...
@@ -332,6 +430,24 @@ void launch_cross_bwd(const void* gout, const void* x0, const void* u,
                      dim3(FIN_COLS * FIN_GROUPS), 0, stream,
                      (const float*)slab, (unsigned short*)bias_grad,
                      (int)num_chunks, N);
+}
+
+void launch_cross_bwd_f32(const void* gout, const void* x0, const void* u,
+                          void* acc, bool init, void* gu, float* slab,
+                          void* bias_grad, int64_t B, int N,
+                          int64_t rows_per_chunk, int64_t num_chunks,
+                          hipStream_t stream) {
+  const int col_tiles = (N + TILE_N_F32 - 1) / TILE_N_F32;
+  dim3 grid(col_tiles, (unsigned)num_chunks);
+  auto kernel =
+      init ? cross_bwd_partial_f32<true> : cross_bwd_partial_f32<false>;
+  hipLaunchKernelGGL(kernel, grid, dim3(COL_LANES * ROW_LANES), 0, stream,
+                     (const float*)gout, (const float*)x0, (const float*)u,
+                     (float*)acc, (float*)gu, slab, B, N, rows_per_chunk);
+  hipLaunchKernelGGL(bias_grad_finish<float>, dim3((N + FIN_COLS - 1) / FIN_COLS),
+                     dim3(FIN_COLS * FIN_GROUPS), 0, stream,
+                     (const float*)slab, (float*)bias_grad, (int)num_chunks,
+                     N);
 }
 
 void launch_relu_bwd_bias_grad_f32(const void* grad_out, const void* y,

@@ -301,6 +301,15 @@ void launch_cross_bwd(const void* gout, const void* x0, const void* u,
                       int64_t rows_per_chunk, int64_t num_chunks,
                       hipStream_t stream);
 
+// The same on fp32 [B, N] with N % 4 == 0, 16-byte aligned, and an fp32
+// bias_grad: gu = gout * x0 (torch's fp32 product), acc = gout * u under
+// init and acc + gout * u otherwise, with one or two roundings.
+void launch_cross_bwd_f32(const void* gout, const void* x0, const void* u,
+                          void* acc, bool init, void* gu, float* slab,
+                          void* bias_grad, int64_t B, int N,
+                          int64_t rows_per_chunk, int64_t num_chunks,
+                          hipStream_t stream);
+
 // cross_ops.hip.  x0 [B, (P+1)*D] = [bottom | packed rows in perm order]:
 // x0[b, 0:D] = bottom[b], x0[b, f*D:(f+1)*D] = packed row perm[f-1] of sample
 // b, at element offset (b*sb + perm[f-1]*sp)*D as in the packed dot
@@ -314,6 +323,17 @@ void launch_cross_concat_fwd(const void* bottom, const void* packed,
 void launch_cross_concat_bwd(const void* gx0, const int* perm, void* gbottom,
                              void* gpacked, int64_t B, int P, int D,
                              int64_t sb, int64_t sp, hipStream_t stream);
+
+// The same assembly on fp32 tensors, D % 4 == 0 and (P+1)*D < 2^26, with D,
+// sb and sp in fp32 elements.
+void launch_cross_concat_f32_fwd(const void* bottom, const void* packed,
+                                 const int* perm, void* x0, int64_t B, int P,
+                                 int D, int64_t sb, int64_t sp,
+                                 hipStream_t stream);
+void launch_cross_concat_f32_bwd(const void* gx0, const int* perm,
+                                 void* gbottom, void* gpacked, int64_t B,
+                                 int P, int D, int64_t sb, int64_t sp,
+                                 hipStream_t stream);
 
 // concat_pool.hip.  out [B, Wp + Nn] = [average pool of the inputs side by
 // side | numerical], window = stride = S, Wp = ceil(W / S), the last window

@@ -17,6 +17,9 @@ kernel's accumulator and not ``L - 1`` extra adds by the autograd engine.
 ``concat_packed`` builds ``x0`` from the bottom MLP's output and the packed
 embeddings (``csrc/cross_ops.hip``).
 
+All three serve two lanes: bf16 tensors under bf16 autocast, and fp32 tensors
+without autocast, on fp32 kernels of their own.
+
 ``DE_FUSED_CROSS=0`` switches the kernels off: the plain composition under
 autograd, and ``index_select`` + ``cat``.
 """
@@ -36,11 +39,19 @@ def _enabled() -> bool:
     return os.environ.get("DE_FUSED_CROSS", "1") != "0" and _backend.available()
 
 
-def _bf16_2d_ok(*ts: torch.Tensor) -> bool:
+def _2d_ok(dtype: torch.dtype, ts) -> bool:
     first = ts[0]
-    return all(t.is_cuda and t.dim() == 2 and t.dtype == torch.bfloat16
+    return all(t.is_cuda and t.dim() == 2 and t.dtype == dtype
                and t.shape == first.shape and t.is_contiguous()
                and t.data_ptr() % 16 == 0 for t in ts)
+
+
+def _bf16_2d_ok(*ts: torch.Tensor) -> bool:
+    return _2d_ok(torch.bfloat16, ts)
+
+
+def _f32_2d_ok(*ts: torch.Tensor) -> bool:
+    return _2d_ok(torch.float32, ts)
 
 
 def cross_bwd(G: torch.Tensor, x0: torch.Tensor, u: torch.Tensor,
@@ -51,10 +62,16 @@ def cross_bwd(G: torch.Tensor, x0: torch.Tensor, u: torch.Tensor,
     One HIP pass for contiguous, 16-byte aligned bf16 ``[B, N]`` GPU tensors
     with ``N % 8 == 0``: ``gu`` equals torch's product bit for bit, ``acc`` is
     formed in fp32 and rounded once, and with ``init`` the old ``acc`` is not
-    read.  The plain torch ops, at any dtype, for anything else.
+    read.  The same pass for fp32 tensors of that kind with ``N % 4 == 0``:
+    ``gu`` and, with ``init``, ``acc`` equal torch's products bit for bit, and
+    ``acc + G * u`` is rounded once or twice.  The plain torch ops, at any
+    dtype, for anything else.
     """
     if (_bf16_2d_ok(G, x0, u, acc) and G.shape[1] % 8 == 0 and _enabled()):
         gu, gb = _backend.ops().cross_bwd(G, x0, u, acc, bool(init))
+        return gu, gb
+    if (_f32_2d_ok(G, x0, u, acc) and G.shape[1] % 4 == 0 and _enabled()):
+        gu, gb = _backend.ops().cross_bwd_f32(G, x0, u, acc, bool(init))
         return gu, gb
     gu = G * x0
     if init:
@@ -80,6 +97,24 @@ class _ConcatPacked(torch.autograd.Function):
         return gbottom, gpacked, None, None
 
 
+class _ConcatPackedF32(torch.autograd.Function):
+    """``_ConcatPacked`` on fp32 tensors."""
+
+    @staticmethod
+    def forward(ctx, bottom, packed, perm, sample_major):
+        ctx.save_for_backward(perm)
+        ctx.sample_major = sample_major
+        return _backend.ops().cross_concat_f32_fwd(bottom, packed, perm,
+                                                   sample_major)
+
+    @staticmethod
+    def backward(ctx, gx0):
+        (perm,) = ctx.saved_tensors
+        gbottom, gpacked = _backend.ops().cross_concat_f32_bwd(
+            gx0.contiguous(), perm, ctx.sample_major)
+        return gbottom, gpacked, None, None
+
+
 def concat_packed(packed: torch.Tensor, bottom: torch.Tensor,
                   perm: torch.Tensor, sample_major: bool = False) -> torch.Tensor:
     """``x0 [B, (P+1)*D] = [bottom | embeddings in model order]``.
@@ -88,6 +123,10 @@ def concat_packed(packed: torch.Tensor, bottom: torch.Tensor,
     ``ops.dot_interact.dot_interact_packed``: ``[P, B, D]`` feature-major or
     ``[B, P, D]`` sample-major, and ``x0[b, f*D:(f+1)*D]`` is packed row
     ``perm[f-1]`` of sample ``b``.  ``perm`` has to be a permutation.
+
+    HIP copy kernels for bf16 GPU tensors with ``D % 8 == 0``, and for fp32
+    GPU tensors with ``D % 4 == 0`` and an int32 ``perm`` on the GPU, both
+    16-byte aligned once contiguous; ``index_select`` + ``cat`` otherwise.
     """
     d = packed.shape[2]
     if (packed.is_cuda and packed.dtype == torch.bfloat16
@@ -95,6 +134,14 @@ def concat_packed(packed: torch.Tensor, bottom: torch.Tensor,
         bottom, packed = bottom.contiguous(), packed.contiguous()
         if bottom.data_ptr() % 16 == 0 and packed.data_ptr() % 16 == 0:
             return _ConcatPacked.apply(bottom, packed, perm, sample_major)
+    elif (packed.is_cuda and bottom.is_cuda and perm.is_cuda
+            and packed.dtype == torch.float32
+            and bottom.dtype == torch.float32 and perm.dtype == torch.int32
+            and d > 0 and d % 4 == 0 and _enabled()):
+        bottom, packed = bottom.contiguous(), packed.contiguous()
+        if bottom.data_ptr() % 16 == 0 and packed.data_ptr() % 16 == 0:
+            return _ConcatPackedF32.apply(bottom, packed, perm.contiguous(),
+                                          sample_major)
     sel = packed.index_select(1, perm.long()) if sample_major else \
         packed.index_select(0, perm.long()).transpose(0, 1)
     return torch.cat([bottom, sel.reshape(bottom.shape[0], -1)], dim=1)
@@ -104,8 +151,9 @@ class _CrossStack(torch.autograd.Function):
     """The whole cross stack, forward and hand-derived backward.
 
     ``apply(x0, dtype, V_0, W_0, b_0, ..., V_{L-1}, W_{L-1}, b_{L-1})`` with
-    ``dtype`` the compute dtype: bf16 under autocast, and float64 on the CPU
-    in the tests, where every step is a torch op.
+    ``dtype`` the compute dtype: bf16 under autocast, fp32 without it (every
+    ``.to(dtype)`` below is then the identity), and float64 on the CPU in the
+    tests, where every step is a torch op.
     """
 
     @staticmethod
@@ -159,7 +207,10 @@ class LowRankCrossNet(nn.Module):
     ``forward(x0)`` returns ``x_L``.  For a 2-D bf16 GPU input under bf16
     autocast, with fp32 parameters, ``N % 8 == 0`` and the HIP extension
     built, the stack runs as one autograd function whose backward uses
-    ``cross_bwd``; everything else is the plain composition under autograd.
+    ``cross_bwd``.  So it does for a 2-D fp32 GPU input with autocast off,
+    fp32 parameters and ``N % 4 == 0``: the same function in fp32, with no
+    casts and the GEMMs of the plain composition.  Everything else (fp32
+    under autocast included) is the plain composition under autograd.
     """
 
     def __init__(self, in_features: int, num_layers: int = 3,
@@ -186,18 +237,24 @@ class LowRankCrossNet(nn.Module):
             out += [v.weight, w.weight, w.bias]
         return out
 
-    def _fused(self, x0: torch.Tensor) -> bool:
-        return (x0.is_cuda and x0.dim() == 2
-                and x0.dtype == torch.bfloat16
-                and torch.is_autocast_enabled()
-                and torch.get_autocast_dtype("cuda") == torch.bfloat16
-                and self.in_features % 8 == 0
-                and all(p.dtype == torch.float32 for p in self._params())
-                and _enabled())
+    def _fused(self, x0: torch.Tensor):
+        """The compute dtype of the whole-stack function, or None."""
+        if not (x0.is_cuda and x0.dim() == 2 and _enabled()
+                and all(p.dtype == torch.float32 for p in self._params())):
+            return None
+        if torch.is_autocast_enabled():
+            if (x0.dtype == torch.bfloat16
+                    and torch.get_autocast_dtype("cuda") == torch.bfloat16
+                    and self.in_features % 8 == 0):
+                return torch.bfloat16
+        elif x0.dtype == torch.float32 and self.in_features % 4 == 0:
+            return torch.float32
+        return None
 
     def forward(self, x0: torch.Tensor) -> torch.Tensor:
-        if self._fused(x0):
-            return _CrossStack.apply(x0, torch.bfloat16, *self._params())
+        dtype = self._fused(x0)
+        if dtype is not None:
+            return _CrossStack.apply(x0, dtype, *self._params())
         x = x0
         for v, w in zip(self.v, self.w):
             u = F.linear(F.linear(x, v.weight), w.weight, w.bias)

@@ -14,8 +14,10 @@ call time, taken with device events:
 
   python tools/bench_cross.py --only fused
   python tools/bench_cross.py --only torch
+  python tools/bench_cross.py --dtype fp32 --only fused
 
---only runs one variant per process; alternate the two to see the
+--dtype fp32 builds fp32 tensors, runs the stack without autocast and counts
+4 bytes per element in the TB/s figure.  --only runs one variant per process; alternate the two to see the
 process-to-process spread.
 """
 import argparse
@@ -52,16 +54,21 @@ def report(name, gbytes, stats):
           flush=True)
 
 
-def bench_op(variant, B, N, rounds, iters):
+DTYPES = {"bf16": torch.bfloat16, "fp32": torch.float32}
+
+
+def bench_op(variant, dtype, B, N, rounds, iters):
     from distributed_embeddings_amd.ops import cross as cross_ops
-    G, x0, u, acc = (torch.randn(B, N, device="cuda").bfloat16()
+    G, x0, u, acc = (torch.randn(B, N, device="cuda").to(dtype)
                      for _ in range(4))
+    gate = cross_ops._bf16_2d_ok if dtype == torch.bfloat16 \
+        else cross_ops._f32_2d_ok
     # bytes the result needs: G, x0, u (and acc) read, gu and acc written
     passes = {True: 5, False: 6}
     for init in (True, False):
-        gb = passes[init] * B * N * 2 / 1e9
+        gb = passes[init] * B * N * G.element_size() / 1e9
         if variant == "fused":
-            assert cross_ops._bf16_2d_ok(G, x0, u, acc) and cross_ops._enabled()
+            assert gate(G, x0, u, acc) and cross_ops._enabled()
 
         # the accumulating form adds a few hundred unit-variance terms over
         # the run: acc stays finite
@@ -70,15 +77,19 @@ def bench_op(variant, B, N, rounds, iters):
         report(f"cross_bwd {variant:5s} init={int(init)}", gb, stats)
 
 
-def bench_net(variant, B, N, r, layers, rounds, iters):
+def bench_net(variant, dtype, B, N, r, layers, rounds, iters):
     from distributed_embeddings_amd.ops.cross import LowRankCrossNet
     net = LowRankCrossNet(N, num_layers=layers, low_rank=r).cuda()
-    x0 = torch.randn(B, N, device="cuda").bfloat16().requires_grad_(True)
-    gout = torch.randn(B, N, device="cuda").bfloat16()
+    x0 = torch.randn(B, N, device="cuda").to(dtype).requires_grad_(True)
+    gout = torch.randn(B, N, device="cuda").to(dtype)
     params = list(net.parameters())
+    bf16 = dtype == torch.bfloat16
+    if not bf16:
+        assert (net._fused(x0) is not None) == (variant == "fused")
 
     def fn():
-        with torch.autocast("cuda", dtype=torch.bfloat16):
+        # fp32 runs without autocast
+        with torch.autocast("cuda", dtype=torch.bfloat16, enabled=bf16):
             out = net(x0)
         torch.autograd.grad(out, [x0] + params, gout)
 
@@ -94,16 +105,22 @@ def main():
     p.add_argument("--layers", type=int, default=3)
     p.add_argument("--rounds", type=int, default=7)
     p.add_argument("--iters", type=int, default=20)
+    p.add_argument("--dtype", choices=tuple(DTYPES), default="bf16",
+                   help="bf16: under bf16 autocast; fp32: fp32 tensors, no "
+                        "autocast")
     args = p.parse_args()
     assert torch.cuda.is_available(), "needs a GPU: no timing without one"
     torch.manual_seed(0)
-    print(f"B={args.batch} N={args.width} r={args.rank} L={args.layers}")
+    dtype = DTYPES[args.dtype]
+    print(f"B={args.batch} N={args.width} r={args.rank} L={args.layers} "
+          f"dtype={args.dtype}")
     variants = ("fused", "torch") if args.only == "all" else (args.only,)
     for variant in variants:
         os.environ["DE_FUSED_CROSS"] = "1" if variant == "fused" else "0"
-        bench_op(variant, args.batch, args.width, args.rounds, args.iters)
-        bench_net(variant, args.batch, args.width, args.rank, args.layers,
-                  args.rounds, args.iters)
+        bench_op(variant, dtype, args.batch, args.width, args.rounds,
+                 args.iters)
+        bench_net(variant, dtype, args.batch, args.width, args.rank,
+                  args.layers, args.rounds, args.iters)
 
 
 if __name__ == "__main__":
